@@ -9,21 +9,27 @@ One "step" = one pass of the whole path over this rank's block of keyframes:
 with every input already resident in HBM (search records packed before the timed region).
 
 `value` is measured on BASELINE.json configs[1] -- 640x480, 64 keyframes x 20 covisible neighbours, synthetic gradient
-images -- in steady state (after a 0.3 s pre-warm phase; the same W + K steps straight after set-up are reported as
-value_cold / ms_per_step_cold / roofline.frac_cold).  At N=1 the same JSON line carries `extra_configs`: the
-north_star's target case (640x480 x 256 keyframes, N=20), configs[2] (1280x720 x 256 keyframes, N=7), configs[1] with two
-outlier neighbours per keyframe (K1 only), configs[1] on i.i.d.-noise images (SURVEY.md §8d adversarial set) and
-configs[1] with a long baseline (10 px/keyframe), each with its own ms_per_step, K1 roofline and mean scan length.
+images -- in steady state (after a 0.3 s pre-warm phase).  A plain run does only that: set-up, pre-warm, W warm-up
+steps, K timed steps, the result line (`roofline` and `stage_ms_per_step` come from the timed steps' own HIP events).
+--full adds everything else: the same W + K steps straight after set-up (value_cold / ms_per_step_cold /
+roofline.frac_cold), live PMC traffic, scan statistics, host upload and streaming rates, the CPU baseline, the other
+exchange forms at N>1 and, at N=1, `extra_configs`: the north_star's target case (640x480 x 256 keyframes, N=20),
+configs[2] (1280x720 x 256 keyframes, N=7), configs[1] with two outlier neighbours per keyframe (K1 only), configs[1] on
+i.i.d.-noise images (SURVEY.md §8d adversarial set) and configs[1] with a long baseline (10 px/keyframe), each with its
+own ms_per_step, K1 roofline and mean scan length.
 Weak scaling: every rank owns --kfs keyframes of one N*kfs sequence (--independent: one separate sequence per GPU,
 configs[4]).
+
+--dump-outputs DIR writes what the last timed step left for rank 0's keyframes (the maps a caller downloads) as .npy files;
+the scene is seeded, so the same arguments give the same inputs on every run.
 
 `python bench.py --gpus N` with N>1 starts its own `torch.distributed.run` child (before anything touches the GPU) when it
 was not launched by one; the line printed is the child's.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel k_search_fuse + its follow-up k_fuse_open, HIP events on
 the engine's stream, algorithmic bytes P*(17+9N) per keyframe; `bound` = what the counters say limits it),
-`step_roofline` (all kernels' algorithmic bytes over the step time) and `cpu_baseline` (the CPU oracle timed on this
-box's host cores on a bounded sample; a reported baseline, not the target).
+`step_roofline` (all kernels' algorithmic bytes over the step time) and, with --full, `cpu_baseline` (the CPU oracle
+timed on this box's host cores on a bounded sample; a reported baseline, not the target).
 """
 import argparse
 import hashlib
@@ -43,6 +49,8 @@ BASELINE_CONFIG = {("480p", 64, 20): "BASELINE.json configs[1]",
                    ("480p", 256, 20): "north_star target case",
                    ("720p", 256, 7): "BASELINE.json configs[2]",
                    ("480p", 8, 7): "BASELINE.json configs[0] geometry"}
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of maps; above it every keyframe gets the same pixel sample
+DUMP_SEED = 0x5EED00D0
 
 
 def parse():
@@ -86,6 +94,13 @@ def parse():
                          "profiling form of the extra_configs outlier line)")
     ap.add_argument("--independent", action="store_true",
                     help="N>1: one independent sequence per GPU, no exchange (BASELINE.json configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (cold steps, live PMC traffic, scan statistics, "
+                         "host upload and streaming rates, CPU baseline, other exchange forms, extra_configs); the --no-* "
+                         "and --cpu-kfs options trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the maps the last step left for rank 0's keyframes to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of pixels when the whole maps exceed %d MiB)" % (DUMP_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -278,24 +293,26 @@ PREWARM_S = 0.3  # the GPU's clocks and caches need ~0.2 s of work to settle (to
 
 
 def prewarm(wl, barrier, exchange, transport, reduce_max=None):
-    """steady-state clocks before the contract's W warm-up steps: untimed steps for about PREWARM_S seconds.  The
-    step count is derived from the (max over ranks) time of the first four steps, so that every rank runs the same
-    number of collective steps."""
+    """steady-state clocks before the contract's W warm-up steps: untimed steps, in rounds of 8, until PREWARM_S seconds
+    have passed (at most 400 steps).  Every round ends in a synchronize and the elapsed time is the max over ranks, so
+    every rank runs the same number of collective steps.  The clock starts after one step: without --full nothing has
+    launched the kernels yet, and the first launches load code objects; the clocks are still ramping after that, so a
+    step count sized from the first steps' time would fall short of PREWARM_S."""
+    wl.step(exchange, transport)
     barrier()
+    # counter passes: every dispatch is serialised and read out, and clocks do not change byte counts
+    budget = 8 if os.environ.get("SDM_BENCH_PMC_CHILD") else 400
     t0 = time.perf_counter()
-    for _ in range(4):
-        wl.step(exchange, transport)
-    wl.torch.cuda.synchronize()
-    t = (time.perf_counter() - t0) / 4
-    if reduce_max is not None:
-        t = reduce_max(t)
-    n = int(min(400, max(4, PREWARM_S / max(t, 1e-5))))
-    if os.environ.get("SDM_BENCH_PMC_CHILD"):
-        n = 4  # counter passes: every dispatch is serialised and read out, and clocks do not change byte counts
-    for _ in range(n):
-        wl.step(exchange, transport)
-    wl.torch.cuda.synchronize()
-    return n + 4
+    n = 0
+    while n < budget:
+        for _ in range(8):
+            wl.step(exchange, transport)
+        n += 8
+        wl.torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        if (reduce_max(t) if reduce_max is not None else t) >= PREWARM_S:
+            break
+    return n + 1
 
 
 def timed(wl, steps, warmup, barrier, exchange, transport):
@@ -356,15 +373,43 @@ def step_roofline(wl, ms_step):
                     "pixels the reference touches (PM.cc:201, 662); their own counters are in profiles/"}
 
 
-def measure(wl, steps, warmup, barrier, exchange, transport, reduce_max=None):
-    """the contract's W warm-up + K timed steps twice: straight after set-up (cold clocks: *_cold) and again after the
-    pre-warm phase (steady state: the figures `value` / `roofline` report)"""
-    dt_c, timing_c = timed(wl, steps, warmup, barrier, exchange, transport)
+def measure(wl, steps, warmup, barrier, exchange, transport, reduce_max=None, cold=True):
+    """the contract's W warm-up + K timed steps after the pre-warm phase (steady state: the figures `value` / `roofline`
+    report); cold: the same W + K steps before that as well, straight after set-up (cold clocks: *_cold; else None)"""
+    dt_c, timing_c = timed(wl, steps, warmup, barrier, exchange, transport) if cold else (None, None)
     n_pre = prewarm(wl, barrier, exchange, transport, reduce_max)
     dt, timing = timed(wl, steps, warmup, barrier, exchange, transport)
     if reduce_max is not None:
-        dt_c, dt = reduce_max(dt_c), reduce_max(dt)
+        dt = reduce_max(dt)
+        if cold:
+            dt_c = reduce_max(dt_c)
     return dt, timing, dt_c, timing_c, n_pre
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: the maps the last step left in this rank's own keyframes, stacked in keyframe order -- rho.npy,
+    sigma.npy [n_kf, px] (after K3) and, unless only K1 is stepped, checked_rho.npy [n_kf, px] (K4) and xyz.npy
+    [n_kf, px, 3] (K5).  px is every pixel in row-major order, or a sorted sample drawn with DUMP_SEED when the maps would
+    exceed DUMP_BYTES."""
+    import numpy as np
+    eng, slots, P = wl.eng, wl.pl["own_slots"], wl.P
+    k1_only = bool(wl.outliers)
+    names = ("rho", "sigma") if k1_only else ("rho", "sigma", "checked_rho", "xyz")
+    bytes_per_px = 8 if k1_only else 24
+    n_px = max(1, min(P, DUMP_BYTES // (bytes_per_px * len(slots))))
+    px = np.arange(P) if n_px == P else np.sort(np.random.default_rng(DUMP_SEED).choice(P, n_px, replace=False))
+    out = {n: [] for n in names}
+    for s in slots:
+        r, sg = eng.download_depth(s)
+        maps = {"rho": r.reshape(P), "sigma": sg.reshape(P)}
+        if not k1_only:
+            maps["checked_rho"] = eng.download_checked(s).reshape(P)
+            maps["xyz"] = eng.download_pointset(s).reshape(P, 3)
+        for n in names:
+            out[n].append(maps[n][px])
+    os.makedirs(out_dir, exist_ok=True)
+    for n in names:
+        np.save(os.path.join(out_dir, n + ".npy"), np.stack(out[n]))
 
 
 def committed_traffic(res, kfs, nbrs, disparity, k1_launches, steps, noise=False, outliers=0, spread=0.1, strip=False, roll=1.0):
@@ -443,7 +488,12 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
-    live, live_note = (None, "multi-rank run") if (args.gpus > 1 or args.independent) else live_traffic(args)
+    if args.gpus > 1 or args.independent:
+        live, live_note = None, "multi-rank run"
+    elif not args.full:
+        live, live_note = None, "live PMC passes run with --full only"
+    else:
+        live, live_note = live_traffic(args)
 
     import torch
     import torch.distributed as dist
@@ -486,10 +536,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # host copies of the images feed only --full's legs (host upload and streaming rates, CPU baseline): none without it
     wl = Workload(pkg, torch, args.res, args.kfs, args.nbrs, args.disparity, world, rank, local_rank,
                   independent=args.independent, noise=args.noise, outliers=(args.outliers if world == 1 else 0),
                   spread=args.prior_spread, strip=(args.scene == "strip"), roll=args.roll,
-                  keep_images=max(args.cpu_kfs + 2 * args.nbrs, min(args.kfs, 64)) if (rank == 0 and world == 1) else 0)
+                  keep_images=max(args.cpu_kfs + 2 * args.nbrs, min(args.kfs, 64)) if (args.full and rank == 0 and world == 1)
+                  else 0)
     eng, pl, W, H, N, P = wl.eng, wl.pl, wl.W, wl.H, wl.N, wl.P
     n_total = wl.n_total * (world if args.independent else 1)
     arch = eng.arch()
@@ -597,7 +649,7 @@ def main():
             streaming = {"error": repr(e)}
         gc.enable()
 
-    stats = None if args.no_stats else wl.scan_stats()  # untimed counting variant of K1
+    stats = wl.scan_stats() if args.full and not args.no_stats else None  # untimed counting variant of K1
 
     def reduce_max(dt):
         if world > 1:
@@ -607,9 +659,11 @@ def main():
         return dt
 
     dt, timing, dt_cold, timing_cold, n_prewarm = measure(wl, args.steps, args.warmup, barrier, args.exchange, transport,
-                                                          reduce_max if world > 1 else None)
+                                                          reduce_max if world > 1 else None, cold=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
     exchange_ms, others = None, {}
-    if exchanging:  # the other exchange forms, same K steps, so the line carries all three
+    if exchanging and args.full:  # the other exchange forms, same K steps, so the line carries all three
         exchange_ms = {args.exchange: round(dt / args.steps * 1e3, 4)}
         for other in ("allgather", "allgather_late", "allgather_full", "halo"):
             if other == args.exchange:
@@ -642,9 +696,10 @@ def main():
     else:
         rf, k1_avg_ms = roofline(wl, timing, args.steps, committed)
         rf["traffic_note"] = live_note
-    rf_cold, _ = roofline(wl, timing_cold, args.steps, None)
-    rf["frac_cold"] = rf_cold["frac"]  # the same K steps after only the W warm-up steps (no pre-warm phase)
-    rf["launch_ms_cold"] = rf_cold["launch_ms"]
+    if timing_cold is not None:
+        rf_cold, _ = roofline(wl, timing_cold, args.steps, None)
+        rf["frac_cold"] = rf_cold["frac"]  # the same K steps after only the W warm-up steps (no pre-warm phase)
+        rf["launch_ms_cold"] = rf_cold["launch_ms"]
     if not exchanging:
         xdesc = "no exchange (%s)" % ("1 GPU" if world == 1 else "independent sequences")
     else:
@@ -660,9 +715,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_step, 4),
-        # the same W + K steps run straight after set-up, before the pre-warm phase (clocks / caches not settled)
-        "ms_per_step_cold": round(dt_cold / args.steps * 1e3, 4),
-        "value_cold": round(P * n_total * args.steps / dt_cold / 1e6, 2),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -691,6 +743,10 @@ def main():
         "roofline": rf,
         "step_roofline": step_roofline(wl, ms_step),
     }
+    if dt_cold is not None:
+        # the same W + K steps run straight after set-up, before the pre-warm phase (clocks / caches not settled)
+        out["ms_per_step_cold"] = round(dt_cold / args.steps * 1e3, 4)
+        out["value_cold"] = round(P * n_total * args.steps / dt_cold / 1e6, 2)
     if exchange_ms:
         out["exchange_ms_per_step"] = exchange_ms
         for other, dt2 in others.items():
@@ -726,7 +782,7 @@ def main():
         out["scan"] = scan_record(stats, k1_avg_ms)
 
     # ---- CPU baseline: the oracle (a port; the reference itself cannot be built) on a bounded sample
-    if args.cpu_kfs > 0 and world == 1:  # rank 0 at N = 1 only
+    if args.full and args.cpu_kfs > 0 and world == 1:  # rank 0 at N = 1 only
         out["cpu_baseline"] = cpu_baseline(args, wl)
     out["gen_s"] = round(wl.t_gen, 2)
     if upload_ms is not None:
@@ -748,8 +804,8 @@ def main():
         out["value_pcie_inclusive_per_keyframe_calls"] = incl(upload_ms["per_keyframe_calls"])
 
     # ---- the other single-GPU BASELINE workloads, each measured like the headline one ----------------------
-    if world == 1 and not args.no_extra and (args.res, args.kfs, args.nbrs, args.prior_spread, args.scene, args.roll) == (
-            "480p", 64, 20, 0.1, "plane", 1.0):
+    if args.full and world == 1 and not args.no_extra and (args.res, args.kfs, args.nbrs, args.prior_spread, args.scene,
+                                                           args.roll) == ("480p", 64, 20, 0.1, "plane", 1.0):
         wl.close()
         extra = []
         xs = max(5, args.steps // 2)

@@ -9,7 +9,7 @@ AHEAD=2 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t
 python3 tools/debug/streaming_account.py $OUT/tr 10 | tee $OUT/account.txt
 python3 tools/debug/streaming_block_dump.py $OUT/tr > $OUT/block.txt 2>&1
 rm -rf $OUT/tr
-timeout -k 10 300 python3 bench.py --no-extra --cpu-kfs 0 > $OUT/bench.json 2> $OUT/bench.err || tail -5 $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full --no-extra --cpu-kfs 0 > $OUT/bench.json 2> $OUT/bench.err || tail -5 $OUT/bench.err
 python3 -c "
 import json; d=json.load(open('$OUT/bench.json'))
 print({k:d[k] for k in d if k.startswith('value') or k=='ms_per_step'}); print(d.get('host_upload'))"
