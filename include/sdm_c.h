@@ -172,6 +172,45 @@ int sdm_upload_depth(sdm_ctx *ctx, int slot, const float *rho, const float *sigm
 int sdm_download_depth(sdm_ctx *ctx, int slot, float *rho, float *sigma); /* depth_map_/depth_sigma_ */
 int sdm_download_checked(sdm_ctx *ctx, int slot, float *rho);
 int sdm_download_pointset(sdm_ctx *ctx, int slot, float *xyz);            /* H x 3W */
+/* ---- the filtered semi-dense point cloud ----------------------------------------------------------- */
+/* The points every consumer of a finished keyframe keeps (SavePointCloudObj PM.cc:100-132, the transcript writer,
+ * the adapter's hand-over): pixel (y, x) passes iff !((double)sigma > max_sigma) && (double)rho > min_rho -- a NaN
+ * sigma passes, a NaN rho fails; the reference's values are max_sigma = 0.01, min_rho = 0.000001.  Extracted on the
+ * device so that only the points cross the link, in the host loops' order: the slots in the order given, raster
+ * order within each.  Bit-identical to the filter applied to sdm_download_depth / _checked / _pointset.
+ * Any field pointer may be NULL (at least one must not be). */
+typedef struct {
+    float *xyz;          /* [capacity][3] world point (SemiDensePointSets_), or NULL */
+    unsigned *pixel;     /* [capacity] (y << 16) | x, or NULL */
+    float *rho_sigma;    /* [capacity][2] the rho that passed and its sigma, or NULL */
+    uint8_t *intensity;  /* [capacity] im(y,x), or NULL */
+    long long capacity;  /* points the buffers hold */
+    int on_device;       /* 1: the pointers are device memory of this context's GPU */
+} sdm_point_buffers;
+
+/* Points of n slots that pass !(sigma > max_sigma) && rho > min_rho, slot order then raster order.
+ * offsets[n+1] (host) receives each slot's first point; offsets[n] = total.
+ * source: where rho comes from -- 1 = the checked plane (what SemiDenseReconBlock downloads into depth_map_),
+ * 0 = the depth map; sigma is always the depth map's.  xyz is copied from the point-set plane as stored.
+ * SDM_EINVAL: null ctx / out / offsets, no field requested, bad or repeated slot, and total > capacity (offsets
+ * are filled, no point is written: size the buffers and call again).  SDM_ESTATE: a slot without a depth map,
+ * source = 1 on a slot never inter-keyframe checked, xyz on a context without with_pointset.
+ * With on_device = 1, SDM_EINVAL also for xyz / pixel not 4-byte and rho_sigma not 8-byte aligned.
+ * Queued on the context's stream; one host wait in the middle (the total), host destinations (pageable or
+ * sdm_host_alloc) are filled by one copy per field of exactly total points from an engine-owned staging buffer;
+ * returns after a stream sync.  Like every compute call, it first waits for the list lengths of its slots if an
+ * upload's read-back of them is still in flight (the tiles are cut on the host).  Changes no plane, flag, list or
+ * counter.
+ * Cost: a slot whose rho plane is zero outside its active list (maps of SemiDenseRecon) is walked through the list
+ * when a zero rho fails (min_rho >= 0), any other slot pixel by pixel over W x H.  Each pass (count, write) reads per walked pixel 8 B {rho,sigma}
+ * + 4 B checked rho (source 1) + 4 B list entry (list walk): 32 B per listed pixel over both passes at source 1;
+ * each written point reads 12 B xyz (+ 16 B record line for intensity) and writes 12 + 4 + 8 + 1 B for the four
+ * fields, which is also what crosses the link for a host destination. */
+int sdm_extract_points(sdm_ctx *ctx, int n, const int *slots, int source, double max_sigma, double min_rho,
+                       sdm_point_buffers *out, long long *offsets);
+/* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
+ * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
+int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);
 /* device addresses for zero-copy interop (RCCL all-gather of per-keyframe {rho,sigma} maps):
  * the depth pool is [max_keyframes][H][W] of float2 {rho,sigma}. */
 void *sdm_depth_pool_ptr(sdm_ctx *ctx);

@@ -34,6 +34,16 @@ class Stats(C.Structure):
                 ("table_stagings", C.c_longlong)]
 
 
+class PointBuffers(C.Structure):
+    """sdm_point_buffers"""
+    _fields_ = [("xyz", C.c_void_p), ("pixel", C.c_void_p), ("rho_sigma", C.c_void_p), ("intensity", C.c_void_p),
+                ("capacity", C.c_longlong), ("on_device", C.c_int)]
+
+
+# sdm_extract_points fields: (dtype, values per point)
+POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
+
+
 def lib_path():
     # SDM_LIB_PATH: A/B a differently-built engine (kernel experiments); still a HIP library
     return os.environ.get("SDM_LIB_PATH") or os.path.join(_HERE, "lib", "libsdm_hip.so")
@@ -76,6 +86,9 @@ SYMBOLS = [
     ("sdm_download_depth", C.c_int, [_ctx, C.c_int, _f32p, _f32p]),
     ("sdm_download_checked", C.c_int, [_ctx, C.c_int, _f32p]),
     ("sdm_download_pointset", C.c_int, [_ctx, C.c_int, _f32p]),
+    ("sdm_extract_points", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.POINTER(PointBuffers),
+                                     C.POINTER(C.c_longlong)]),
+    ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
     ("sdm_mark_depth_present", C.c_int, [_ctx, C.c_int, _ip]),
@@ -186,6 +199,7 @@ class Engine:
         cfg.ext_depth_pool = ext_depth_pool
         cfg.stream = stream
         self.W, self.H, self.max_keyframes, self.max_neighbours = W, H, max_keyframes, max_neighbours
+        self.device = device
         self.ctx = _ctx()
         self._check(self.lib.sdm_create(C.byref(self.ctx), C.byref(cfg)))
 
@@ -396,6 +410,69 @@ class Engine:
         x = np.empty((self.H, 3 * self.W), np.float32)
         self._check(self.lib.sdm_download_pointset(self.ctx, slot, x.ctypes.data_as(_f32p)))
         return x
+
+    def extract_points(self, slots, source=1, max_sigma=0.01, min_rho=1e-6, fields=("xyz",), out=None):
+        """The filtered semi-dense cloud of `slots` (sdm_extract_points): points with !(sigma > max_sigma) and
+        rho > min_rho, slot order then raster order.  Returns {field: array of the points, "offsets": int64[n+1]}.
+        fields: any of xyz [m,3] f32, pixel [m] u32 ((y << 16) | x), rho_sigma [m,2] f32, intensity [m] u8.
+        out: {field: preallocated array} -- NumPy (pageable, or pinned from host_alloc) or torch device tensors (all of
+        one kind); the returned arrays are views of their first `total` points.  Too small: SdmError with .offsets.
+        Without out the buffers are sized by extract_bound: the list length of the slots walked by list, W*H of the others."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        n = len(sl)
+        if out is None:
+            for f in fields:
+                if f not in POINT_FIELDS:
+                    raise ValueError("unknown point field %r" % (f,))
+            cap = max(self.extract_bound(sl, source, min_rho), 1)
+            out = {f: np.empty((cap, POINT_FIELDS[f][1]) if POINT_FIELDS[f][1] > 1 else (cap,), POINT_FIELDS[f][0])
+                   for f in fields}
+        pb = PointBuffers()
+        cap, kinds = None, set()
+        for f, a in out.items():
+            if f not in POINT_FIELDS:
+                raise ValueError("unknown point field %r" % (f,))
+            dt, per = POINT_FIELDS[f]
+            if isinstance(a, np.ndarray):
+                if a.dtype != dt or not a.flags.c_contiguous or a.size % per:
+                    raise ValueError("%s: need a C-contiguous %s array of [m, %d]" % (f, np.dtype(dt).name, per))
+                kinds.add("host")
+                ptr, m = a.ctypes.data, a.size // per
+            else:  # a torch tensor on this engine's device
+                if not (getattr(a, "is_cuda", False) and a.is_contiguous()) or a.element_size() != np.dtype(dt).itemsize:
+                    raise ValueError("%s: need a contiguous device tensor of %d-byte elements" % (f, np.dtype(dt).itemsize))
+                if a.get_device() != self.device:
+                    raise ValueError("%s: tensor on device %d, engine on device %d" % (f, a.get_device(), self.device))
+                kinds.add("device")
+                ptr, m = a.data_ptr(), a.numel() // per
+                align = 8 if f == "rho_sigma" else np.dtype(dt).itemsize  # (the kernel stores {rho, sigma} as one float2)
+                if ptr % align:
+                    raise ValueError("%s: device tensor address not %d-byte aligned" % (f, align))
+            setattr(pb, f, ptr)
+            cap = m if cap is None else min(cap, m)
+        if len(kinds) > 1:
+            raise ValueError("out mixes host arrays and device tensors")
+        pb.capacity = cap if cap is not None else 0
+        pb.on_device = 1 if kinds == {"device"} else 0
+        offs = np.zeros(n + 1, np.int64)
+        rc = self.lib.sdm_extract_points(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma), float(min_rho),
+                                         C.byref(pb), offs.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.offsets = offs
+            raise e
+        total = int(offs[n])
+        res = {f: a[:total] if POINT_FIELDS[f][1] == 1 else a.reshape(-1, POINT_FIELDS[f][1])[:total] for f, a in out.items()}
+        res["offsets"] = offs
+        return res
+
+    def extract_bound(self, slots, source=1, min_rho=1e-6):
+        """the most points extract_points can return for these arguments (sdm_extract_bound)"""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        b = C.c_longlong()
+        self._check(self.lib.sdm_extract_bound(self.ctx, len(sl), sl.ctypes.data_as(_ip), int(source), float(min_rho),
+                                               C.byref(b)))
+        return int(b.value)
 
     def mark_depth_present(self, slots):
         r, rp = _i32(np.asarray(slots).reshape(-1))

@@ -27,6 +27,7 @@
 
 #include "sdm_c.h"
 #include "sdm_kernels.h"
+#include "sdm_extract.h"
 
 using namespace sdm;
 
@@ -226,6 +227,15 @@ struct sdm_ctx {
     int* d_agree = nullptr;  // sdm_comm_all_ok
     int xchg_entries = 0;    // sdm_exchange_compact: > 0 = maps cross ranks as their first xchg_entries active-list entries
     unsigned* d_xchg_mismatch = nullptr;  // compact maps refused by k_unpack_lists (list lengths differ)
+
+    // sdm_extract_points: device work buffer (slot table, tile counts and offsets), pinned mirror of the slot table and
+    // the offsets, and the staging buffer of host destinations; each grows on demand
+    unsigned char* d_ext = nullptr;
+    size_t ext_bytes = 0;
+    unsigned char* h_ext = nullptr;
+    size_t ext_host_bytes = 0;
+    unsigned char* d_ext_stage = nullptr;
+    size_t ext_stage_bytes = 0;
 };
 
 namespace {
@@ -1064,6 +1074,9 @@ void sdm_destroy(sdm_ctx* c)
     }
     (void)hipHostFree(c->h_f2);
     (void)hipHostFree(c->h_act_count);
+    (void)hipFree(c->d_ext);
+    (void)hipFree(c->d_ext_stage);
+    (void)hipHostFree(c->h_ext);
     for (auto& sp : c->spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
@@ -2027,6 +2040,206 @@ int sdm_download_pointset(sdm_ctx* c, int slot, float* xyz)
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipMemcpyAsync(xyz, c->xyz + (long long)slot * c->P * 3, sizeof(float) * 3 * c->P, hipMemcpyDeviceToHost,
                            c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDM_OK;
+}
+
+// ---- filtered point cloud (sdm_extract_points, sdm_extract.h) ----------------------------------------------------------
+// the largest float <= t (NaN for NaN): for every float v, (double)v > t  <=>  v > ext_float_floor(t)
+static float ext_float_floor(double t)
+{
+    const float inf = std::numeric_limits<float>::infinity();
+    if (t != t) return std::numeric_limits<float>::quiet_NaN();
+    if (t >= (double)std::numeric_limits<float>::max()) return t == (double)inf ? inf : std::numeric_limits<float>::max();
+    if (t < -(double)std::numeric_limits<float>::max()) return -inf;
+    float f = (float)t;
+    if ((double)f > t) f = std::nextafterf(f, -inf);
+    return f;
+}
+
+static size_t ext_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// grow a device / pinned buffer to at least `bytes` (the previous call ended with a stream sync: nothing uses it)
+static int ext_grow_dev(unsigned char** p, size_t* have, size_t bytes)
+{
+    if (*have >= bytes) return SDM_OK;
+    HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    HIP_TRY(hipMalloc((void**)p, bytes));
+    *have = bytes;
+    return SDM_OK;
+}
+static int ext_grow_host(unsigned char** p, size_t* have, size_t bytes)
+{
+    if (*have >= bytes) return SDM_OK;
+    HIP_TRY(hipHostFree(*p));
+    *p = nullptr;
+    *have = 0;
+    HIP_TRY(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
+    *have = bytes;
+    return SDM_OK;
+}
+
+// The slots' checks and walks, shared by sdm_extract_points and sdm_extract_bound: count[i] = items of slot i -- its list
+// length when the list walk covers every pixel that can pass, W*H otherwise.  Waits for list lengths still in flight.
+static int ext_plan(sdm_ctx* c, int n, const int* slots, int source, double min_rho, std::vector<char>& use_list,
+                    std::vector<int>& count)
+{
+    if (n < 0 || (n > 0 && !slots)) return fail(SDM_EINVAL, "null or negative slot list");
+    if (source != 0 && source != 1) return fail(SDM_EINVAL, "source must be 0 (depth map) or 1 (checked plane)");
+    std::vector<char> seen((size_t)c->cfg.max_keyframes, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = slots[i];
+        if (s < 0 || s >= c->cfg.max_keyframes) return fail(SDM_EINVAL, "slot out of range");
+        if (seen[(size_t)s]) return fail(SDM_EINVAL, "slot listed twice");
+        seen[(size_t)s] = 1;
+    }
+    for (int i = 0; i < n; i++) {
+        if (!c->has_depth[slots[i]]) return fail(SDM_ESTATE, "slot has no depth map");
+        if (source && !c->has_chk[slots[i]]) return fail(SDM_ESTATE, "slot has not been inter-keyframe checked");
+    }
+    // per slot: the list path when the rho plane is zero outside the list now in d_act (the flags sdm_pointset decides by;
+    // a depth map counts only while the list is the one of the current lambdaG, which this call does not rebuild) and a
+    // zero rho cannot pass (min_rho < 0 keeps the zeros off the list: those slots are walked whole)
+    const bool zero_fails = !(0.0 > min_rho);
+    use_list.assign((size_t)n, 0);
+    count.assign((size_t)n, (int)c->P);
+    std::vector<int> list_slots;
+    for (int i = 0; i < n; i++) {
+        const int s = slots[i];
+        const bool has_list = c->act_lambdaG[s] == c->act_lambdaG[s];
+        use_list[i] = zero_fails && (source ? (c->chk_sparse[s] && has_list)
+                                            : (c->recon_lambdaG[s] == c->dprm.lambdaG && c->act_lambdaG[s] == c->dprm.lambdaG));
+        if (use_list[i]) list_slots.push_back(s);
+    }
+    int rc;
+    if (!list_slots.empty() && (rc = sync_counts_for(c, (int)list_slots.size(), list_slots.data(), 0, nullptr))) return rc;
+    for (int i = 0; i < n; i++)
+        if (use_list[i]) count[i] = c->h_act_count[slots[i]];
+    return SDM_OK;
+}
+
+int sdm_extract_bound(sdm_ctx* c, int n, const int* slots, int source, double min_rho, long long* bound)
+{
+    if (!c || !bound) return fail(SDM_EINVAL, "null argument");
+    std::vector<char> use_list;
+    std::vector<int> count;
+    int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
+    if (rc) return rc;
+    long long b = 0;
+    for (int i = 0; i < n; i++) b += count[i];
+    *bound = b;
+    return SDM_OK;
+}
+
+int sdm_extract_points(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
+                       sdm_point_buffers* out, long long* offsets)
+{
+    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
+    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity) return fail(SDM_EINVAL, "no output field requested");
+    if (out->capacity < 0) return fail(SDM_EINVAL, "negative capacity");
+    if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel) % 4 || (uintptr_t)out->rho_sigma % 8))
+        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel: 4 B; rho_sigma: 8 B)");
+    std::vector<char> use_list;
+    std::vector<int> count;
+    int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
+    if (rc) return rc;
+    if (out->xyz && !c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+
+    const size_t tab_b = ext_align(sizeof(ExtractSlot) * (size_t)std::max(n, 1));
+    const size_t offs_b = ext_align(sizeof(unsigned long long) * (size_t)(n + 1));
+    if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, tab_b + offs_b))) return rc;
+    ExtractSlot* h_tab = reinterpret_cast<ExtractSlot*>(c->h_ext);
+    unsigned long long* h_offs = reinterpret_cast<unsigned long long*>(c->h_ext + tab_b);
+    long long nt = 0;
+    for (int i = 0; i < n; i++) {
+        ExtractSlot& d = h_tab[i];
+        d.tile0 = nt;
+        d.slot = slots[i];
+        d.list = use_list[i] ? 1 : 0;
+        d.count = count[i];
+        d.pad = 0;
+        nt += (d.count + EXT_TILE - 1) / EXT_TILE;
+    }
+    if (nt == 0) {  // nothing to walk: every slot is empty
+        for (int i = 0; i <= n; i++) offsets[i] = 0;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SDM_OK;
+    }
+    const long long nb = (nt + 1 + EXT_SCAN - 1) / EXT_SCAN;  // scan workgroups over the nt + 1 tile offsets
+    if (nb > std::numeric_limits<int>::max() || nt > std::numeric_limits<int>::max())
+        return fail(SDM_EINVAL, "too many tiles in one call");
+    const size_t cnt_b = ext_align(sizeof(unsigned) * (size_t)nt);
+    const size_t toff_b = ext_align(sizeof(unsigned) * (size_t)(nt + 1));
+    const size_t blk_b = ext_align(sizeof(unsigned long long) * (size_t)nb);
+    if ((rc = ext_grow_dev(&c->d_ext, &c->ext_bytes, tab_b + cnt_b + toff_b + 2 * blk_b + offs_b))) return rc;
+    ExtractSlot* d_tab = reinterpret_cast<ExtractSlot*>(c->d_ext);
+    unsigned* d_cnt = reinterpret_cast<unsigned*>(c->d_ext + tab_b);
+    unsigned* d_toff = reinterpret_cast<unsigned*>(c->d_ext + tab_b + cnt_b);
+    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b);
+    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b + blk_b);
+    unsigned long long* d_offs = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b + 2 * blk_b);
+
+    ExtractIn in;
+    in.tab = d_tab;
+    in.n = n;
+    in.pool = c->pool;
+    in.chk = source ? c->chk : nullptr;
+    in.act = c->d_act;
+    in.xyz = c->xyz;
+    in.rec = c->rec;
+    in.P = c->P;
+    in.W = c->W;
+    in.sig_max = ext_float_floor(max_sigma);
+    in.rho_min = ext_float_floor(min_rho);
+    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, sizeof(ExtractSlot) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_cnt);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, d_cnt, nt, d_toff, d_bsum);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)nb, d_boff);
+    hipLaunchKernelGGL(k_extract_offsets, dim3(blocks_for(n + 1)), dim3(BLOCK), 0, c->stream, d_tab, n, nt, d_toff, d_boff,
+                       d_offs);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_offs, d_offs, sizeof(unsigned long long) * (size_t)(n + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the one wait in the middle: the total sizes what follows
+    for (int i = 0; i <= n; i++) offsets[i] = (long long)h_offs[i];
+    const long long total = offsets[n];
+    if (total > out->capacity) return fail(SDM_EINVAL, "capacity " + std::to_string(out->capacity) + " < " +
+                                                           std::to_string(total) + " points (offsets filled)");
+    if (total == 0) return SDM_OK;
+
+    // where pass 3 writes: the caller's device buffers, or one staging region per requested field
+    ExtractOut dst;
+    size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0;
+    if (out->on_device) {
+        dst.xyz = out->xyz;
+        dst.pixel = out->pixel;
+        dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
+        dst.intensity = out->intensity;
+    } else {
+        const size_t t = (size_t)total;
+        size_t at = 0;
+        if (out->xyz) xyz_off = at, at += ext_align(12 * t);
+        if (out->pixel) pix_off = at, at += ext_align(4 * t);
+        if (out->rho_sigma) rs_off = at, at += ext_align(8 * t);
+        if (out->intensity) im_off = at, at += ext_align(t);
+        if ((rc = ext_grow_dev(&c->d_ext_stage, &c->ext_stage_bytes, at))) return rc;
+        unsigned char* b = c->d_ext_stage;
+        dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
+        dst.pixel = out->pixel ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
+        dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
+        dst.intensity = out->intensity ? b + im_off : nullptr;
+    }
+    hipLaunchKernelGGL(k_extract_write, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_toff, d_boff, dst);
+    HIP_TRY(hipGetLastError());
+    if (!out->on_device) {
+        const size_t t = (size_t)total;
+        if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, dst.xyz, 12 * t, hipMemcpyDeviceToHost, c->stream));
+        if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, dst.pixel, 4 * t, hipMemcpyDeviceToHost, c->stream));
+        if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, dst.rho_sigma, 8 * t, hipMemcpyDeviceToHost, c->stream));
+        if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, dst.intensity, t, hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDM_OK;
 }
