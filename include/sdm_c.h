@@ -103,7 +103,8 @@ int sdm_upload_image(sdm_ctx *ctx, int slot, const uint8_t *im, const float K[4]
  * pixels: H*W interleaved pixels of 1, 3 or 4 bytes.  dist = {k1,k2,p1,p2,k3} as in Examples/Monocular/TUM1.yaml
  * (Camera.k1.. ; src/Tracking.cc:65-75), NULL = the frame is already undistorted.  The fork's Modeler converts
  * with CV_RGB2GRAY whatever Camera.RGB says: pass SDM_ORDER_RGB to reproduce that, the true order for a correct gray.
- * OpenCV is absent here: PARITY UNPINNED, the published algorithms restated. */
+ * Bit-exact with OpenCV 2.4.5's cvUndistort2 + cvCvtColor and cvSobel(CV_SCHARR)/32 + cvCartToPolar
+ * (tests/test_gpu_opencv_pin.py). */
 #define SDM_ORDER_RGB 0
 #define SDM_ORDER_BGR 1
 #define SDM_ORDER_RGBA 2
@@ -381,7 +382,10 @@ int sdm_get_timing(sdm_ctx *ctx, double ms_total[SDM_NUM_STAGES], long long laun
  *          random geometries / 2x2 tap patches; out[1] = cases whose fast result was accepted;
  * which 8: scan identities (lerp weight, in-plane-rotation wrap) over all 2^32 float inputs;
  * which 9: the same run as 7, reporting out[1] = projections (PM.cc:677-680, 695) decided by K4's approximate chain --
- *          each compared with the plain-division chain's cell, validity and offset. */
+ *          each compared with the plain-division chain's cell, validity and offset;
+ * which 10: K1's fast_atan2_deg_x1 (PM.cc:414) vs fast_atan2_deg(y, 1) over all 2^32 float inputs; out[1] = an
+ *          order-independent 64-bit digest of its results, equal to OpenCV 2.4.5's cvFastArctan(y, 1)
+ *          (tests/golden/fastatan2_x1_digest.json). */
 int sdm_selftest(sdm_ctx *ctx, int which, unsigned long long out[2]);
 /* name of the device the context runs on, e.g. "gfx950" */
 const char *sdm_device_arch(sdm_ctx *ctx);

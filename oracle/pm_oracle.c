@@ -1,6 +1,6 @@
 /*
  * pm_oracle.c -- CPU ORACLE for the ProbabilityMapping hot path.  TEST INFRASTRUCTURE ONLY.
- * See pm_oracle.h for the rules (who may call this) and the "PARITY UNPINNED" statement.
+ * See pm_oracle.h for the rules (who may call this) and what the parity rests on.
  *
  * Every function cites the lines of /root/reference/src/Modeler/ProbabilityMapping.cc ("PM.cc")
  * it follows.  Arithmetic follows the C++ promotion rules in force in PM.cc:
@@ -15,7 +15,7 @@
  *  N4 sub-pixel refine needs 1 <= u <= W-2 and floor(yf(u+-1)) in [0,H-2], else no hypothesis.
  *  N5 NaN epipolar line or NaN search-range end => no hypothesis (reference: UB int conversion).
  *  N6 bilinear is the 2-tap vertical lerp it degenerates to for integer x (bit-identical, App. A.1).
- *  N7 I_stddev is float; cv::fastAtan2 is the OpenCV-3.x polynomial restated from memory.
+ *  N7 I_stddev is float; cv::fastAtan2's polynomial, bit-exact with OpenCV 2.4.5 (tests/test_opencv_pin.py).
  *  N8 inter-KF check: NaN projection counts as out of bounds; K*X omits the exact-zero terms.
  */
 #include "pm_oracle.h"
@@ -77,8 +77,9 @@ float pmo_fast_atan2(float y, float x)
  * Modeler::AddFrameImage (src/Modeler/Modeler.cc:1496-1514), converted with cvtColor(CV_RGB2GRAY) at its
  * use (src/Modeler/Modeler.cc:154-155); Tracking's own gray: src/Tracking.cc:244-257.  OpenCV is absent:
  * cv::undistort (initUndistortRectifyMap in double -> CV_16SC2 1/32-pixel map -> remap INTER_LINEAR in 15-bit
- * fixed point, BORDER_CONSTANT 0) and RGB2Gray<uchar> (4899/9617/1868 >> 14) restated from memory, with the
- * source position evaluated directly per pixel (OpenCV accumulates it along the row).  PARITY UNPINNED (N9). */
+ * fixed point, BORDER_CONSTANT 0) and RGB2Gray<uchar> (4899/9617/1868 >> 14), with the source position evaluated
+ * directly per pixel (OpenCV accumulates it along the row).  Bit-exact with OpenCV 2.4.5's cvUndistort2 + cvCvtColor
+ * (tests/test_opencv_pin.py, N9). */
 static int ingest_gray(int r, int g, int b) { return (r * 4899 + g * 9617 + b * 1868 + (1 << 13)) >> 14; }
 
 void pmo_ingest(const uint8_t *src, int W, int H, int channels, int r_idx, int g_idx, int b_idx,
@@ -102,13 +103,13 @@ void pmo_ingest(const uint8_t *src, int W, int H, int channels, int r_idx, int g
             const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2);
             const double yd = y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy;
             const double us = fx * xd + cx, vs = fy * yd + cy;
-            double fu = rint(us * 32.0), fv = rint(vs * 32.0); /* saturate_cast<int>: round half to even */
-            if (!(fu > -2147483648.0)) fu = -2147483648.0;
-            if (!(fv > -2147483648.0)) fv = -2147483648.0;
-            if (fu > 2147483647.0) fu = 2147483647.0;
-            if (fv > 2147483647.0) fv = 2147483647.0;
+            /* saturate_cast<int>(double) is cvRound (SSE2 cvtsd2si): round half to even; NaN and out-of-range
+             * values give INT_MIN.  The CV_16SC2 map stores the integer part as a short (wraps modulo 2^16). */
+            double fu = rint(us * 32.0), fv = rint(vs * 32.0);
+            if (!(fu >= -2147483648.0 && fu <= 2147483647.0)) fu = -2147483648.0;
+            if (!(fv >= -2147483648.0 && fv <= 2147483647.0)) fv = -2147483648.0;
             const int iu = (int)fu, iv = (int)fv;
-            const int sx = iu >> 5, sy = iv >> 5, a = iu & 31, b = iv & 31;
+            const int sx = (int16_t)(iu >> 5), sy = (int16_t)(iv >> 5), a = iu & 31, b = iv & 31;
             const int wt[4] = {(32 - a) * (32 - b) * 32, a * (32 - b) * 32, (32 - a) * b * 32, a * b * 32};
             int acc[3] = {0, 0, 0};
             for (int t = 0; t < 4; t++) {

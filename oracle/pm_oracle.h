@@ -11,8 +11,10 @@
  * mismatch) and OpenCV/Eigen are absent from the image, so the reference itself cannot be built
  * or run.  The oracle is therefore pinned only by (a) line-by-line transcription, each function
  * citing the PM.cc lines it follows, and (b) an independent float32 NumPy restatement of the
- * closed-form pieces (tests/test_oracle_crosscheck.py).  Normative choices where the reference
- * has undefined behaviour or un-pinnable third-party arithmetic are listed in DESIGN.md §3.
+ * closed-form pieces (tests/test_oracle_crosscheck.py).  The OpenCV pieces (fastAtan2, Scharr + cartToPolar,
+ * undistort, cvtColor) are pinned bit for bit against OpenCV 2.4.5, which the reference ships prebuilt
+ * (oracle/ref_opencv.py, tests/test_opencv_pin.py).  Normative choices where the reference has undefined
+ * behaviour, or where the build deviates from OpenCV's arithmetic (N1/N2), are listed in DESIGN.md §3.
  *
  * Build: oracle/Makefile  (-O2 -ffp-contract=off -fno-fast-math; results are bit-defined).
  */
@@ -70,11 +72,11 @@ typedef struct {
 
 void pmo_default_params(pmo_params *p);
 
-/* cv::fastAtan2 restated from OpenCV 3.x -- PM.cc:414. */
+/* cv::fastAtan2 -- PM.cc:414; bit-exact with OpenCV 2.4.5. */
 float pmo_fast_atan2(float y, float x);
 
 /* Image ingest (src/Tracking.cc:244-257, 266-271; src/Modeler/Modeler.cc:154-155): undistort the interleaved
- * 1/3/4-channel frame (dist = {k1,k2,p1,p2,k3} or NULL) and convert to gray.  OpenCV absent: parity unpinned. */
+ * 1/3/4-channel frame (dist = {k1,k2,p1,p2,k3} or NULL) and convert to gray.  Bit-exact with OpenCV 2.4.5 (N9). */
 void pmo_ingest(const uint8_t *src, int W, int H, int channels, int r_idx, int g_idx, int b_idx,
                 const float K[4], const float *dist, uint8_t *gray);
 

@@ -2465,6 +2465,8 @@ int sdm_selftest(sdm_ctx* c, int which, unsigned long long out[2])
         hipLaunchKernelGGL(k_selftest_rcp, dim3(4096), dim3(BLOCK), 0, c->stream, c->d_stats + 5, c->d_stats + 6);
     } else if (which == 8) {
         hipLaunchKernelGGL(k_selftest_scan_ids, dim3(4096), dim3(BLOCK), 0, c->stream, c->d_stats + 5, c->d_stats + 6);
+    } else if (which == 10) {
+        hipLaunchKernelGGL(k_selftest_atan_x1, dim3(4096), dim3(BLOCK), 0, c->stream, c->d_stats + 5, c->d_stats + 6);
     } else if (which == 3) {
         hipLaunchKernelGGL(k_selftest_gates, dim3(4096), dim3(BLOCK), 0, c->stream, c->dprm, c->d_stats + 5, c->d_stats + 6);
     } else {

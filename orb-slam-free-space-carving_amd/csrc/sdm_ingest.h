@@ -88,14 +88,13 @@ __global__ __launch_bounds__(BLOCK) void k_ingest_batch(const IngestItem* __rest
     const double xd = x * kr + q.p1 * _2xy + q.p2 * (r2 + 2 * x2);
     const double yd = y * kr + q.p1 * (r2 + 2 * y2) + q.p2 * _2xy;
     const double us = q.fx * xd + q.cx, vs = q.fy * yd + q.cy;
-    // saturate_cast<int>(double) = round half to even, clamped; a NaN position lands outside the image
+    // saturate_cast<int>(double) is cvRound (SSE2 cvtsd2si): round half to even; NaN and out-of-range values give INT_MIN.
+    // The CV_16SC2 map stores the integer part as a short (wraps modulo 2^16), as OpenCV 2.4.5 does (tests/test_opencv_pin.py).
     double fu = rint(us * 32.0), fv = rint(vs * 32.0);
-    if (!(fu > -2147483648.0)) fu = -2147483648.0;
-    if (!(fv > -2147483648.0)) fv = -2147483648.0;
-    if (fu > 2147483647.0) fu = 2147483647.0;
-    if (fv > 2147483647.0) fv = 2147483647.0;
+    if (!(fu >= -2147483648.0 && fu <= 2147483647.0)) fu = -2147483648.0;
+    if (!(fv >= -2147483648.0 && fv <= 2147483647.0)) fv = -2147483648.0;
     const int iu = (int)fu, iv = (int)fv;
-    const int sx = iu >> 5, sy = iv >> 5, a = iu & 31, b = iv & 31;
+    const int sx = (short)(iu >> 5), sy = (short)(iv >> 5), a = iu & 31, b = iv & 31;
     const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
     int acc[3] = {0, 0, 0};
     const int idx[3] = {ch == 1 ? 0 : q.r_idx, ch == 1 ? 0 : q.g_idx, ch == 1 ? 0 : q.b_idx};

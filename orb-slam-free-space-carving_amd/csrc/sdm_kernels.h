@@ -1912,6 +1912,35 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_scan_ids(unsigned long long*
     }
 }
 
+// which = 10: K1's fast_atan2_deg_x1 (PM.cc:414) vs fast_atan2_deg(y, 1.0f) over EVERY float bit pattern y.  bad =
+// mismatches (NaN matches NaN); aux = an order-independent digest of fast_atan2_deg_x1's results: the sum mod 2^64 over
+// the patterns i of SplitMix64(i << 32 | bits(result)), a NaN result counted as 0x7fc00000.  The same sum of OpenCV
+// 2.4.5's cvFastArctan(y, 1) is recorded in tests/golden/fastatan2_x1_digest.json (tests/cv_pin.py states it).
+__global__ __launch_bounds__(BLOCK) void k_selftest_atan_x1(unsigned long long* __restrict__ bad,
+                                                            unsigned long long* __restrict__ digest)
+{
+    unsigned long long cnt = 0, dig = 0;
+    const unsigned long long stride = (unsigned long long)gridDim.x * BLOCK;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < (1ull << 32); i += stride) {
+        const float y = __uint_as_float((unsigned)i);
+        const float got = fast_atan2_deg_x1(y), want = fast_atan2_deg(y, 1.0f);
+        const bool nan = got != got;
+        if (!(__float_as_uint(got) == __float_as_uint(want) || (nan && want != want))) cnt++;
+        unsigned long long z = (i << 32) | (nan ? 0x7fc00000u : __float_as_uint(got));
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        dig += z ^ (z >> 31);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_down(cnt, o);
+        dig += __shfl_down(dig, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (cnt) atomicAdd(bad, cnt);
+        atomicAdd(digest, dig);
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_selftest_chi(int iters, unsigned long long* __restrict__ bad,
                                                         unsigned long long* __restrict__ inband)
 {

@@ -6,29 +6,31 @@ oracle/pm_oracle.c: the scan loop + sub-pixel refinement (PM.cc:385-465), the hy
 (486-547) and the inter-keyframe check with its Gauss-Newton step (628-799).  Vectorised over the
 pixels of one keyframe; every operation is an elementwise IEEE float32/float64 NumPy operation in the
 order and precision the C++ promotion rules give, so it can be compared with the
-C oracle bit for bit (tests/test_oracle_second_restatement.py).  The reference holds no vectors
-(parity unpinned); two restatements by different routes agreeing bit for bit is what bounds
+C oracle bit for bit (tests/test_oracle_second_restatement.py).  The reference holds no vectors for
+this path; two restatements by different routes agreeing bit for bit is what bounds
 transcription error.
 
 Two arithmetic modes for the pieces that live inside OpenCV in the reference:
 
   mode="n1"  the build's normative choice N1/N2: 3x3 / 3x1 products in float,
              accumulated left to right; `A*B/s`, `A*B*s + C` as separate float operations.
-  mode="cv"  OpenCV-3.x cv::Mat expression semantics, RESTATED FROM MEMORY (OpenCV is absent from the
-             image, so this cannot be checked against the library):
-             * a product with a transposed operand (`Rcw2*Rcw1.t()`, PM.cc:859) and any product whose
-               result is 1x1 (`R21.row(2)*xp`, `J.t()*r0`) take cv::gemm's general path: products and
-               sums in double, scaled by alpha in double, rounded to float once;
+  mode="cv"  OpenCV 2.4.5's cvGEMM / cvInvert / cvConvertScale arithmetic, PINNED against the library
+             (the reference ships it prebuilt; tests/test_opencv_pin.py drives the helpers below against it):
+             * a product with a transposed operand (`Rcw2*Rcw1.t()`, PM.cc:859, GEMM_2_T; `J.t()*r0`,
+               `J.t()*J`, GEMM_1_T) and any product whose result is 1x1 (`R21.row(2)*xp`) take cv::gemm's
+               general path: products and sums in double, scaled by alpha in double, rounded to float once;
              * a plain 3x3*3x3 or 3x3*3x1 product takes cv::gemm's small-matrix path: the dot product
                is accumulated in FLOAT left to right, then `(float)(t*alpha + c*beta)` is evaluated
                in double -- so `R21*xp*mind + t21` (PM.cc:894) and `Rji*xp/depthp + tji` (PM.cc:678)
                fold their scale (mind, resp. the DOUBLE reciprocal 1.0/depthp) and the addition into
                one rounding;
-             * `Xj/Xj(2)` (PM.cc:680) is a multiplication by (float)(1.0/(double)Xj(2));
+             * `Xj/Xj(2)` (PM.cc:680) is convertTo: x * (float)(1.0/(double)Xj(2)) + 0.0f in float;
              * K.inv() of a 3x3 float matrix is the adjugate evaluated in double, rounded once.
-The "cv" mode exists to MEASURE how much the un-pinnable OpenCV rounding could move results
-(tests/test_oracle_second_restatement.py reports mask flips and ulp distances); "n1" is what the
-oracle and the engine implement.
+             NOT pinned: how cv::MatExpr folds an expression such as `A*B/s + C` into ONE gemm call (alpha,
+             beta, flags).  The C API cannot reach MatExpr; the folds above are read from PM.cc's expressions
+             and stay an assumption.  OpenCV 3.x is not on hand.
+The "cv" mode MEASURES how far N1 is from what OpenCV 2.4.5 computes (tests/test_oracle_second_restatement.py
+reports mask flips and ulp distances on every golden fixture); "n1" is what the oracle and the engine implement.
 """
 import math
 
@@ -482,8 +484,8 @@ def inter_check(cur, cur_rho, nbrs, pairs, nbr_rho, nbr_sigma):
             u = kj.fx * tmp[0] + kj.cx * tmp[2]
             v = kj.fy * tmp[1] + kj.cy * tmp[2]
             if mode == "cv":
-                sc = (1.0 / f64(tmp[2])).astype(f32)             # Xj/Xj(2): convertTo with (float)(1./s)
-                xj, yj = u * sc, v * sc
+                sc = (1.0 / f64(tmp[2])).astype(f32)             # Xj/Xj(2): convertTo, x * (float)(1./s) + 0.0f
+                xj, yj = u * sc + f32(0), v * sc + f32(0)
             else:
                 xj, yj = u / tmp[2], v / tmp[2]                  # PM.cc:680
             depthj = depthp / (rzxp + depthp * t[2])             # PM.cc:684-688

@@ -1,7 +1,8 @@
 """GPU: sdm_upload_image_rgb (device colour->gray + lens undistortion feeding the gradient pre-pass; SURVEY.md §8f-1,
 src/Tracking.cc:244-257, 266-271, src/Modeler/Modeler.cc:154-155) against the oracle's restatement, bit for bit --
 the gray image, the derived GradImg / GradTheta / I_stddev, and the whole path run from colour frames.
-PARITY UNPINNED for the OpenCV pieces (absent from the image): both sides state the same published algorithm."""
+The OpenCV pieces are pinned against OpenCV 2.4.5 itself, oracle and device alike: tests/test_opencv_pin.py,
+tests/test_gpu_opencv_pin.py."""
 import ctypes as C
 
 import numpy as np

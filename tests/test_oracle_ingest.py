@@ -1,8 +1,8 @@
 """CPU: the image-ingest restatement (oracle/pm_oracle.c pmo_ingest: lens undistortion + colour->gray as the fork
 applies them before the path, src/Tracking.cc:244-257, 266-271 and src/Modeler/Modeler.cc:154-155).
 
-OpenCV is absent from the image, so this is PARITY UNPINNED: cv::undistort and cvtColor's published 8-bit
-algorithms restated from memory.  What is checked: known answers of the gray weights (the values OpenCV documents
+cv::undistort and cvtColor are pinned bit for bit against OpenCV 2.4.5 in tests/test_opencv_pin.py (every colour,
+every calibration the reference ships, far-outside positions).  What is checked here, without the library: known answers of the gray weights (the values OpenCV documents
 for pure primaries), identity behaviour, an independent vectorised NumPy restatement bit for bit, and the geometry
 (an undistorted straight-line scene is straight)."""
 import numpy as np

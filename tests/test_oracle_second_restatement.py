@@ -8,9 +8,9 @@ hypothesis (PM.cc:385-465, 806-875), the search range (877-910), the hypothesis 
 intra-keyframe check (486-547) and growing (549-596), and the inter-keyframe check with its Gauss-Newton step
 (628-799).  The closed-form pieces have their own cross-check in test_oracle_crosscheck.py.
 
-The last test bounds what "unpinned" can cost: the same restatement with OpenCV's cv::Mat rounding semantics
-(restated from memory) instead of the build's normative float algebra; tools/cv_mode_report.py prints the full
-table quoted in DESIGN.md §3."""
+The last tests measure what N1/N2 cost: the same restatement with OpenCV 2.4.5's cv::gemm / invert / convertTo rounding
+(np_pm mode="cv", pinned against the library in test_opencv_pin.py) instead of the build's normative float algebra, on
+every golden fixture; tools/cv_mode_report.py prints the table (profiles/cv_mode_opencv245_report.md)."""
 import numpy as np
 import pytest
 
@@ -98,18 +98,36 @@ def test_second_restatement_growing_on_crafted_maps(oracle):
     assert (wr != rho).sum() > 10, "the crafted maps must make the growing step do something"
 
 
-def test_cv_rounding_mode_moves_no_support(pkg, oracle):
-    """What "parity unpinned" can cost: OpenCV cv::Mat / cv::gemm rounding (restated from memory, np_pm mode="cv")
-    instead of the normative float algebra (N1/N2).  On this fixture: no support-mask flip at any stage, and the
-    values move by about one float ulp (stated bounds: p99 of the relative difference < 1e-5, fewer than 0.1 % of
-    the supported pixels move by more than 1e-4 -- those are arg-min / tap choices that tip over)."""
+def _cv_mode_cost(pkg, oracle, name):
     import os
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import cv_mode_report
-    g = gu.load("plane_64x48_n7")
+    g = gu.load(name)
     seq = gu.sequence_from(pkg, oracle, g)
-    res = cv_mode_report.run(seq, g["n"], list(range(seq.n_kf)))
+    return cv_mode_report.run(seq, g["n"], list(range(seq.n_kf)))
+
+
+@pytest.mark.parametrize("name", [n for n in gu.fixture_names() if n != "plane_64x48_n7"])
+def test_cv_rounding_mode_on_every_fixture(pkg, oracle, name):
+    """the bounds of test_cv_rounding_mode_moves_no_support on the other golden fixtures
+    (profiles/cv_mode_opencv245_report.md)"""
+    res = _cv_mode_cost(pkg, oracle, name)
+    for stage, s in res.items():
+        assert s["support"] > 5000, stage
+        assert s["mask_flips"] <= 0.001 * s["support"], (stage, s)
+        assert s["rel_p99"] < 1e-5, (stage, s)
+        assert s["over_1e4"] <= 0.001 * s["support"], (stage, s)
+    assert res["K1 rho (search+fusion)"]["values_differ"] > 1000, "the two modes must actually differ"
+
+
+def test_cv_rounding_mode_moves_no_support(pkg, oracle):
+    """What N1/N2 cost against OpenCV 2.4.5: its cv::gemm / invert / convertTo rounding (np_pm mode="cv", pinned against
+    the library by tests/test_opencv_pin.py; only cv::MatExpr's folding stays assumed) instead of the normative float
+    algebra.  On this fixture: no support-mask flip at any stage, and the values move by about one float ulp (stated
+    bounds: p99 of the relative difference < 1e-5, fewer than 0.1 % of the supported pixels move by more than 1e-4 --
+    those are arg-min / tap choices that tip over).  All four fixtures: profiles/cv_mode_opencv245_report.md."""
+    res = _cv_mode_cost(pkg, oracle, "plane_64x48_n7")
     for stage, s in res.items():
         assert s["support"] > 5000, stage
         assert s["mask_flips"] <= 0.001 * s["support"], (stage, s)

@@ -1,9 +1,9 @@
-"""How far could OpenCV's cv::Mat rounding move the results?  ("parity unpinned")
+"""How far does OpenCV 2.4.5's cv::gemm / invert / convertTo rounding move the results from N1/N2?  
 
 Runs the NumPy restatement of PM.cc (tests/np_pm.py) in its two arithmetic modes on the golden fixtures and
 on a keyframe of BASELINE.json configs[1] (640x480, N = 20):
   n1  float left-to-right small-matrix algebra -- what the oracle and the engine implement (bit-equal to both);
-  cv  OpenCV-3.x MatExpr / cv::gemm semantics restated from memory (OpenCV is absent from the image).
+  cv  OpenCV 2.4.5's cvGEMM / cvInvert / cvConvertScale rounding, pinned against the library (tests/test_opencv_pin.py).
 Reports support-mask flips and the distribution of relative differences per stage.  Test infrastructure.
 
     python tools/cv_mode_report.py            # prints a markdown table
