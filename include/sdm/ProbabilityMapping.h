@@ -129,6 +129,10 @@ struct Options {
     std::string obj_path = "semi_pointcloud.obj"; /* written when Run() ends, PM.cc:100 */
     unsigned poll_us = 5000;         /* Run()'s usleep, PM.cc:87 */
     bool exchange_compact = true;    /* sharded passes: maps cross ranks as their active-list entries (sdm_exchange_compact) */
+    /* SemiDenseRecon / SemiDenseReconBlock derive the median in-plane rotations and the depth bounds (PM.cc:170-184) on the
+     * device: one sdm_upload_observations_batch of every keyframe of the call, then sdm_search_priors.  The same values
+     * as the host helpers; a call whose upload is refused falls back to them. */
+    bool device_priors = false;
 };
 
 }  // namespace sdm
@@ -222,6 +226,7 @@ private:
     bool Ensure(int W, int H);
     void PushDepth(sdm::KeyFrame* kf, int slot);
     std::vector<sdm::KeyFrame*> PickNeighbours(sdm::KeyFrame* kf);  /* PM.cc:151-160 */
+    bool UploadObservations(const std::vector<sdm::KeyFrame*>& kfs, const std::vector<int>& slots); /* device_priors */
     static std::vector<sdm::KeyFrame*> PickNeighboursN(sdm::KeyFrame* kf, int covisN);
 
     bool CheckFinish();

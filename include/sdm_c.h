@@ -34,6 +34,7 @@ extern "C" {
 #define SDM_ECOMM 5    /* RCCL error or library not loadable (text in sdm_last_error) */
 
 #define SDM_MAX_NEIGHBOURS 64
+#define SDM_MAX_OBSERVATIONS 8192 /* keypoints / point depths per keyframe (sdm_upload_observations*) */
 
 typedef struct sdm_ctx sdm_ctx;
 
@@ -146,6 +147,40 @@ int sdm_intra_check(sdm_ctx *ctx, int n_ref, const int *ref_slots);     /* PM.cc
 int sdm_intra_grow(sdm_ctx *ctx, int n_ref, const int *ref_slots);      /* PM.cc:549-596 */
 int sdm_recon(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n, const int *nbr_slots,
               const float *rot_deg, const float *min_depth, const float *max_depth);
+
+/* ---- search priors from the keyframes' ORB observations, on the device -------------------------
+ * What SemiDenseRecon derives before its search: the median in-plane rotation of every (reference, neighbour) pair
+ * (GetRotInPlane + median, PM.cc:170-179 and 467-484) and the inverse-depth bounds of every reference
+ * (StereoSearchConstraints, PM.cc:184 and 370-383), equal to sdm_median_rot_in_plane (as floats, -0 == +0) and bitwise
+ * equal to sdm_stereo_search_constraints.
+ *
+ * A slot holds its keyframe's observations as sdm::KeyFrame carries them: map_point_ids[n_kp] (< 0 = no map point),
+ * angles[n_kp] (mvKeysUn[i].angle, degrees, < 0 = no angle), depths[n_depths] (GetAllPointDepths()).  Only entries with
+ * id >= 0 && angle >= 0 are kept, sorted by id on the device.  Order: upload the slot's image FIRST -- every image upload
+ * into a slot (sdm_upload_keyframe, sdm_upload_image*, the batch and device variants) marks its observations absent.
+ * Memory: nothing until the first observation upload; then 12 * SDM_MAX_OBSERVATIONS + 8 bytes per slot
+ * (96 KiB; 6 MiB for 64 slots) plus staging buffers that grow with the largest call.
+ *
+ * Refused with SDM_EINVAL, that slot's observations left absent and the batch's other keyframes stored: n_kp or n_depths
+ * above SDM_MAX_OBSERVATIONS, a non-negative id that appears twice (the host helper would emit the cross product; the
+ * fork never holds one map point at two keypoints, MapPoint.cc:103-106 and 209-216), a NaN or infinite angle.  A bad
+ * argument (null pointer, negative count, slot out of range, a slot twice in one batch) refuses the whole call before
+ * anything changes.  Arrays may be NULL where their count is 0.  Host-blocking (one status read-back); every caller
+ * buffer is free on return. */
+int sdm_upload_observations(sdm_ctx *ctx, int slot, int n_kp, const int *map_point_ids, const float *angles,
+                            int n_depths, const float *depths);
+/* n keyframes in one packed host-to-device copy and one kernel launch */
+int sdm_upload_observations_batch(sdm_ctx *ctx, int n, const int *slots, const int *n_kp,
+                                  const int *const *map_point_ids, const float *const *angles, const int *n_depths,
+                                  const float *const *depths);
+/* rot_deg [n_ref][n] (may be NULL), min_depth / max_depth [n_ref] (may be NULL): host arrays, written on return.
+ * SDM_ESTATE for a slot without observations; SDM_EINVAL for a reference without depths when a bound is asked for
+ * (the host helper's n <= 0 refusal), n outside [1, max_neighbours], a slot out of range.  One copy in, one launch,
+ * one copy out, then a stream synchronise: the host needs the priors before K1 is set up. */
+int sdm_search_priors(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n, const int *nbr_slots, float *rot_deg,
+                      float *min_depth, float *max_depth);
+/* sdm_search_priors + sdm_recon: the same maps as sdm_recon fed the host helpers' values */
+int sdm_recon_observed(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n, const int *nbr_slots);
 
 /* ---- InterKeyFrameDepthChecking, PM.h:91 / PM.cc:628-799 -------------------------------------- */
 /* Reads the neighbours' current {rho,sigma}; writes the checked rho of each reference keyframe to

@@ -8,6 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 MAX_NEIGHBOURS = 64
+MAX_OBSERVATIONS = 8192  # SDM_MAX_OBSERVATIONS
 
 
 class SdmError(RuntimeError):
@@ -79,6 +80,11 @@ SYMBOLS = [
     ("sdm_intra_check", C.c_int, [_ctx, C.c_int, _ip]),
     ("sdm_intra_grow", C.c_int, [_ctx, C.c_int, _ip]),
     ("sdm_recon", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, _f32p, _f32p, _f32p]),
+    ("sdm_upload_observations", C.c_int, [_ctx, C.c_int, C.c_int, _ip, _f32p, C.c_int, _f32p]),
+    ("sdm_upload_observations_batch", C.c_int, [_ctx, C.c_int, _ip, _ip, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _ip,
+                                                C.POINTER(C.c_void_p)]),
+    ("sdm_search_priors", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, _f32p, _f32p, _f32p]),
+    ("sdm_recon_observed", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip]),
     ("sdm_inter_check", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int]),
     ("sdm_pointset", C.c_int, [_ctx, C.c_int, _ip, C.c_int]),
     ("sdm_inter_check_pointset", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int]),
@@ -362,6 +368,54 @@ class Engine:
     def recon(self, refs, nbrs, min_depth, max_depth, rot=None):
         """SemiDenseRecon (PM.h:75) for a batch of reference keyframes."""
         self._stage(self.lib.sdm_recon, refs, nbrs, rot, min_depth, max_depth)
+
+    # -- search priors from ORB observations (sdm_upload_observations*, sdm_search_priors) ------------------------------
+    def upload_observations(self, slot, map_point_ids, angles, depths):
+        """one keyframe's GetMapPointMatches ids (< 0 = none), keypoint angles (< 0 = none) and GetAllPointDepths()"""
+        i, ip = _i32(np.asarray(map_point_ids).reshape(-1))
+        a, ap = _f32(np.asarray(angles).reshape(-1))
+        d, dp = _f32(np.asarray(depths).reshape(-1))
+        if len(i) != len(a):
+            raise ValueError("map_point_ids and angles differ in length")
+        self._check(self.lib.sdm_upload_observations(self.ctx, int(slot), len(i), ip, ap, len(d), dp))
+
+    def upload_observations_batch(self, slots, map_point_ids, angles, depths):
+        """lists of per-keyframe arrays, one packed copy"""
+        n = len(slots)
+        ids = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in map_point_ids]
+        ang = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32) for x in angles]
+        dep = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float32) for x in depths]
+        assert len(ids) == n and len(ang) == n and len(dep) == n
+        if any(len(x) != len(y) for x, y in zip(ids, ang)):
+            raise ValueError("map_point_ids and angles differ in length")
+        sl, slp = _i32(np.asarray(slots).reshape(-1))
+        nk, nkp = _i32([len(x) for x in ids])
+        nd, ndp = _i32([len(x) for x in dep])
+        P = C.c_void_p * max(n, 1)
+        pi = P(*[x.ctypes.data if len(x) else None for x in ids])
+        pa = P(*[x.ctypes.data if len(x) else None for x in ang])
+        pd = P(*[x.ctypes.data if len(x) else None for x in dep])
+        self._check(self.lib.sdm_upload_observations_batch(self.ctx, n, slp, nkp, pi, pa, ndp, pd))
+
+    def search_priors(self, refs, nbrs):
+        """(rot [n_ref, n], min_depth [n_ref], max_depth [n_ref]) from the slots' observations, float32"""
+        refs = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        n_ref = len(refs)
+        nbrs = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(n_ref, -1)
+        n = nbrs.shape[1]
+        rot = np.empty((n_ref, n), np.float32)
+        mn = np.empty(n_ref, np.float32)
+        mx = np.empty(n_ref, np.float32)
+        self._check(self.lib.sdm_search_priors(self.ctx, n_ref, refs.ctypes.data_as(_ip), n, nbrs.ctypes.data_as(_ip),
+                                               rot.ctypes.data_as(_f32p), mn.ctypes.data_as(_f32p), mx.ctypes.data_as(_f32p)))
+        return rot, mn, mx
+
+    def recon_observed(self, refs, nbrs):
+        """recon() with the priors derived on the device from the slots' observations (sdm_recon_observed)"""
+        refs = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        nbrs = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(len(refs), -1)
+        self._check(self.lib.sdm_recon_observed(self.ctx, len(refs), refs.ctypes.data_as(_ip), nbrs.shape[1],
+                                                nbrs.ctypes.data_as(_ip)))
 
     def intra_check(self, refs):
         r, rp = _i32(np.asarray(refs).reshape(-1))

@@ -28,6 +28,7 @@
 #include "sdm_c.h"
 #include "sdm_kernels.h"
 #include "sdm_extract.h"
+#include "sdm_priors.h"
 
 using namespace sdm;
 
@@ -236,6 +237,15 @@ struct sdm_ctx {
     size_t ext_host_bytes = 0;
     unsigned char* d_ext_stage = nullptr;
     size_t ext_stage_bytes = 0;
+
+    // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
+    ObsStore obs{};                 // obs.cap != 0 once allocated
+    std::vector<char> has_obs;      // [max_keyframes] the slot holds accepted observations (cleared by reset_slot_state)
+    std::vector<int> obs_kp, obs_nd;  // [max_keyframes] keypoints / depths of the last accepted upload
+    unsigned char *d_obs_stage = nullptr, *h_obs_stage = nullptr;  // packed upload block (+ status words on the device)
+    size_t obs_dev_bytes = 0, obs_host_bytes = 0;
+    unsigned char *d_pri = nullptr, *h_pri = nullptr;  // sdm_search_priors: slot tables in, priors out
+    size_t pri_dev_bytes = 0, pri_host_bytes = 0;
 };
 
 namespace {
@@ -750,6 +760,7 @@ void reset_slot_state(sdm_ctx* c, int slot)
     c->act_lambdaG[slot] = std::nanf("");
     c->chk_sparse[slot] = 1;
     c->xyz_sparse[slot] = 1;
+    if (!c->has_obs.empty()) c->has_obs[slot] = 0;  // a recycled slot never lends its old keyframe's observations
 }
 // ... and the planes (the image paths clear them inside k_prepass_batch instead)
 int reset_slot(sdm_ctx* c, int slot)
@@ -1077,6 +1088,15 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->d_ext);
     (void)hipFree(c->d_ext_stage);
     (void)hipHostFree(c->h_ext);
+    (void)hipFree(c->obs.ids);
+    (void)hipFree(c->obs.ang);
+    (void)hipFree(c->obs.depth);
+    (void)hipFree(c->obs.cnt);
+    (void)hipFree(c->obs.nd);
+    (void)hipFree(c->d_obs_stage);
+    (void)hipHostFree(c->h_obs_stage);
+    (void)hipFree(c->d_pri);
+    (void)hipHostFree(c->h_pri);
     for (auto& sp : c->spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
@@ -2411,6 +2431,205 @@ float sdm_median_rot_in_plane(const int* mp1, const float* angle1, int n1, const
     if (rot.empty()) return 0.f;  // PM.cc:174-177
     std::sort(rot.begin(), rot.end());
     return rot[(rot.size() - 1) / 2];
+}
+
+// ---- search priors from resident ORB observations (sdm_priors.h) ---------------------------------------------------------
+static int obs_alloc(sdm_ctx* c)
+{
+    if (c->obs.cap) return SDM_OK;
+    const int K = c->cfg.max_keyframes;
+    const size_t per = (size_t)K * SDM_MAX_OBSERVATIONS;
+    int rc;
+    if ((!c->obs.ids && (rc = dev_alloc(&c->obs.ids, per))) || (!c->obs.ang && (rc = dev_alloc(&c->obs.ang, per))) ||
+        (!c->obs.depth && (rc = dev_alloc(&c->obs.depth, per))) || (!c->obs.cnt && (rc = dev_alloc(&c->obs.cnt, (size_t)K))) ||
+        (!c->obs.nd && (rc = dev_alloc(&c->obs.nd, (size_t)K))))
+        return rc;
+    // the sort holds a keyframe's ids and angles in LDS: 64 KB at the cap
+    HIP_TRY(hipFuncSetAttribute((const void*)k_obs_ingest, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(2 * sizeof(unsigned) * SDM_MAX_OBSERVATIONS)));
+    c->has_obs.assign(K, 0);
+    c->obs_kp.assign(K, 0);
+    c->obs_nd.assign(K, 0);
+    c->obs.cap = SDM_MAX_OBSERVATIONS;
+    return SDM_OK;
+}
+
+static int upload_observations_impl(sdm_ctx* c, int n, const int* slots, const int* n_kp, const int* const* ids,
+                                    const float* const* angles, const int* n_depths, const float* const* depths)
+{
+    int rc = check_batch_slots(c, n, slots);
+    if (rc) return rc;
+    if (n == 0) return SDM_OK;
+    if (!n_kp || !ids || !angles || !n_depths || !depths) return fail(SDM_EINVAL, "null argument");
+    for (int i = 0; i < n; i++) {
+        if (n_kp[i] < 0 || n_depths[i] < 0) return fail(SDM_EINVAL, "negative observation count");
+        if ((n_kp[i] > 0 && (!ids[i] || !angles[i])) || (n_depths[i] > 0 && !depths[i]))
+            return fail(SDM_EINVAL, "null observation array");
+    }
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = obs_alloc(c))) return rc;
+    // a keyframe over the cap is refused (its observations become absent); the others are stored
+    std::string why;
+    std::vector<int> take;
+    size_t words = 0;
+    int sort_max = 1;
+    for (int i = 0; i < n; i++) {
+        c->has_obs[slots[i]] = 0;
+        if (n_kp[i] > SDM_MAX_OBSERVATIONS || n_depths[i] > SDM_MAX_OBSERVATIONS) {
+            if (why.empty()) why = "slot " + std::to_string(slots[i]) + ": more than SDM_MAX_OBSERVATIONS entries";
+            continue;
+        }
+        take.push_back(i);
+        words += 2 * (size_t)n_kp[i] + (size_t)n_depths[i];
+        int s = 1;
+        while (s < n_kp[i]) s <<= 1;
+        sort_max = std::max(sort_max, s);
+    }
+    const int m = (int)take.size();
+    if (m > 0) {
+        const size_t item_bytes = ext_align(sizeof(ObsItem) * m);
+        const size_t data_bytes = ext_align(4 * words);
+        if ((rc = ext_grow_host(&c->h_obs_stage, &c->obs_host_bytes, item_bytes + data_bytes)) ||
+            (rc = ext_grow_dev(&c->d_obs_stage, &c->obs_dev_bytes, item_bytes + data_bytes + sizeof(int) * m)))
+            return rc;
+        ObsItem* items = (ObsItem*)c->h_obs_stage;
+        long long off = (long long)(item_bytes / 4);
+        for (int t = 0; t < m; t++) {
+            const int i = take[t];
+            ObsItem& it = items[t];
+            it.slot = slots[i];
+            it.n_kp = n_kp[i];
+            it.n_depths = n_depths[i];
+            int s = 1;
+            while (s < n_kp[i]) s <<= 1;
+            it.sort_n = s;
+            it.off = off;
+            unsigned char* dst = c->h_obs_stage + 4 * off;
+            if (n_kp[i]) {
+                memcpy(dst, ids[i], 4 * (size_t)n_kp[i]);
+                memcpy(dst + 4 * (size_t)n_kp[i], angles[i], 4 * (size_t)n_kp[i]);
+            }
+            if (n_depths[i]) memcpy(dst + 8 * (size_t)n_kp[i], depths[i], 4 * (size_t)n_depths[i]);
+            off += 2LL * n_kp[i] + n_depths[i];
+        }
+        int* d_status = (int*)(c->d_obs_stage + item_bytes + data_bytes);
+        HIP_TRY(hipMemcpyAsync(c->d_obs_stage, c->h_obs_stage, item_bytes + 4 * words, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_obs_ingest, dim3(m), dim3(OBS_BLOCK), 2 * sizeof(unsigned) * sort_max, c->stream,
+                           (const ObsItem*)c->d_obs_stage, (const unsigned char*)c->d_obs_stage, c->obs, d_status);
+        HIP_TRY(hipGetLastError());
+        int* h_status = (int*)c->h_obs_stage;  // (the items are no longer needed on the host)
+        HIP_TRY(hipMemcpyAsync(h_status, d_status, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int t = 0; t < m; t++) {
+            const int i = take[t], st = h_status[t];
+            if (st) {
+                if (why.empty())
+                    why = "slot " + std::to_string(slots[i]) +
+                          ((st & OBS_BAD_DUPLICATE) ? ": a map point id appears twice" : ": NaN or infinite keypoint angle");
+                continue;
+            }
+            c->has_obs[slots[i]] = 1;
+            c->obs_kp[slots[i]] = n_kp[i];
+            c->obs_nd[slots[i]] = n_depths[i];
+        }
+    }
+    if (!why.empty()) return fail(SDM_EINVAL, "observations refused, " + why);
+    return SDM_OK;
+}
+
+int sdm_upload_observations_batch(sdm_ctx* c, int n, const int* slots, const int* n_kp, const int* const* map_point_ids,
+                                  const float* const* angles, const int* n_depths, const float* const* depths)
+{
+    try {
+        return upload_observations_impl(c, n, slots, n_kp, map_point_ids, angles, n_depths, depths);
+    } catch (const std::exception& e) {
+        return fail(SDM_EHIP, std::string("observations: ") + e.what());
+    }
+}
+
+int sdm_upload_observations(sdm_ctx* c, int slot, int n_kp, const int* map_point_ids, const float* angles, int n_depths,
+                            const float* depths)
+{
+    return sdm_upload_observations_batch(c, 1, &slot, &n_kp, &map_point_ids, &angles, &n_depths, &depths);
+}
+
+static int search_priors_impl(sdm_ctx* c, int n_ref, const int* ref_slots, int n, const int* nbr_slots, float* rot,
+                              float* mind, float* maxd)
+{
+    if (!c) return fail(SDM_EINVAL, "null context");
+    if (n_ref <= 0 || !ref_slots) return fail(SDM_EINVAL, "n_ref <= 0 or null ref_slots");
+    if (n < 1 || n > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n out of [1, max_neighbours]");
+    if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
+    const bool want_depth = mind || maxd;
+    int rc;
+    for (int r = 0; r < n_ref; r++)
+        for (int j = -1; j < n; j++) {
+            const int s = j < 0 ? ref_slots[r] : nbr_slots[(size_t)r * n + j];
+            if ((rc = check_slot(c, s, false))) return rc;
+            if (c->has_obs.empty() || !c->has_obs[s]) return fail(SDM_ESTATE, "slot " + std::to_string(s) + " has no observations");
+        }
+    if (want_depth)
+        for (int r = 0; r < n_ref; r++)
+            if (c->obs_nd[ref_slots[r]] == 0)
+                return fail(SDM_EINVAL, "reference slot " + std::to_string(ref_slots[r]) + " has no point depths");
+    if (!rot && !want_depth) return SDM_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t np = (size_t)n_ref * n;
+    const size_t in_bytes = ext_align(sizeof(int) * (n_ref + np));
+    const size_t out_words = np + 2 * (size_t)n_ref;
+    if ((rc = ext_grow_host(&c->h_pri, &c->pri_host_bytes, in_bytes + sizeof(float) * out_words)) ||
+        (rc = ext_grow_dev(&c->d_pri, &c->pri_dev_bytes, in_bytes + sizeof(float) * out_words)))
+        return rc;
+    memcpy(c->h_pri, ref_slots, sizeof(int) * n_ref);
+    memcpy(c->h_pri + sizeof(int) * n_ref, nbr_slots, sizeof(int) * np);
+    int max_kp = 1;
+    for (int r = 0; r < n_ref; r++) max_kp = std::max(max_kp, c->obs_kp[ref_slots[r]]);
+    float* d_out = (float*)(c->d_pri + in_bytes);
+    PriorArgs a;
+    a.st = c->obs;
+    a.refs = (const int*)c->d_pri;
+    a.nbrs = a.refs + n_ref;
+    a.rot = d_out;
+    a.mind = d_out + np;
+    a.maxd = d_out + np + n_ref;
+    a.n_ref = n_ref;
+    a.n = n;
+    a.depth_blocks = want_depth ? n_ref : 0;
+    const long long blocks = a.depth_blocks + (rot ? (long long)np : 0);
+    HIP_TRY(hipMemcpyAsync(c->d_pri, c->h_pri, sizeof(int) * (n_ref + np), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_priors, dim3((unsigned)blocks), dim3(OBS_BLOCK), sizeof(unsigned) * max_kp, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    float* h_out = (float*)(c->h_pri + in_bytes);
+    HIP_TRY(hipMemcpyAsync(h_out, d_out, sizeof(float) * out_words, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (rot) memcpy(rot, h_out, sizeof(float) * np);
+    if (mind) memcpy(mind, h_out + np, sizeof(float) * n_ref);
+    if (maxd) memcpy(maxd, h_out + np + n_ref, sizeof(float) * n_ref);
+    return SDM_OK;
+}
+
+int sdm_search_priors(sdm_ctx* c, int n_ref, const int* ref_slots, int n, const int* nbr_slots, float* rot_deg,
+                      float* min_depth, float* max_depth)
+{
+    try {
+        return search_priors_impl(c, n_ref, ref_slots, n, nbr_slots, rot_deg, min_depth, max_depth);
+    } catch (const std::exception& e) {
+        return fail(SDM_EHIP, std::string("search priors: ") + e.what());
+    }
+}
+
+int sdm_recon_observed(sdm_ctx* c, int n_ref, const int* ref_slots, int n, const int* nbr_slots)
+{
+    if (!c) return fail(SDM_EINVAL, "null context");
+    if (n_ref <= 0 || n < 1) return fail(SDM_EINVAL, "n_ref <= 0 or n < 1");
+    try {
+        std::vector<float> rot((size_t)n_ref * n), mind(n_ref), maxd(n_ref);
+        int rc = sdm_search_priors(c, n_ref, ref_slots, n, nbr_slots, rot.data(), mind.data(), maxd.data());
+        if (rc) return rc;
+        return sdm_recon(c, n_ref, ref_slots, n, nbr_slots, rot.data(), mind.data(), maxd.data());
+    } catch (const std::exception& e) {
+        return fail(SDM_EHIP, std::string("recon observed: ") + e.what());
+    }
 }
 
 // ---- instrumentation ------------------------------------------------------------------------------------------------------------

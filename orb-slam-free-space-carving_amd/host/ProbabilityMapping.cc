@@ -235,6 +235,26 @@ void ProbabilityMapping::StereoSearchConstraints(sdm::KeyFrame* kf, float* min_d
         report("StereoSearchConstraints");
 }
 
+// Options::device_priors: the keyframes' current observations (ids and depths change with culling and bundle adjustment) to
+// their slots in one copy; false when the engine refuses one (e.g. a map point at two keypoints) -- the caller then derives
+// the priors with the host helpers
+bool ProbabilityMapping::UploadObservations(const std::vector<sdm::KeyFrame*>& kfs, const std::vector<int>& slots)
+{
+    const int n = (int)kfs.size();
+    std::vector<int> n_kp(n), n_depths(n);
+    std::vector<const int*> ids(n);
+    std::vector<const float*> angles(n), depths(n);
+    for (int i = 0; i < n; i++) {
+        n_kp[i] = (int)std::min(kfs[i]->map_point_ids.size(), kfs[i]->keypoint_angles.size());  // as the host helper reads them
+        ids[i] = kfs[i]->map_point_ids.data();
+        angles[i] = kfs[i]->keypoint_angles.data();
+        n_depths[i] = (int)kfs[i]->point_depths.size();
+        depths[i] = kfs[i]->point_depths.data();
+    }
+    return sdm_upload_observations_batch(ctx_, n, slots.data(), n_kp.data(), ids.data(), angles.data(), n_depths.data(),
+                                         depths.data()) == SDM_OK;
+}
+
 // PM.cc:137-256 (per-keyframe reconstruction) followed by PM.cc:262-315 (inter-keyframe checking of
 // every keyframe whose neighbours are all reconstructed).
 void ProbabilityMapping::SemiDenseRecon(sdm::KeyFrame* kf)
@@ -245,21 +265,32 @@ void ProbabilityMapping::SemiDenseRecon(sdm::KeyFrame* kf)
     const int ref = SlotOf(kf);
     if (ref < 0) return;
     std::vector<int> nslots;
-    std::vector<float> rot;
     for (size_t j = 0; j < nbrs.size(); j++) {
         int s = SlotOf(nbrs[j]);
         if (s < 0) return;
         nslots.push_back(s);
-        // PM.cc:170-179: median in-plane rotation over shared map points, 0 without covisibility
-        rot.push_back(sdm_median_rot_in_plane(kf->map_point_ids.data(), kf->keypoint_angles.data(),
-                                              (int)std::min(kf->map_point_ids.size(), kf->keypoint_angles.size()),
-                                              nbrs[j]->map_point_ids.data(), nbrs[j]->keypoint_angles.data(),
-                                              (int)std::min(nbrs[j]->map_point_ids.size(),
-                                                            nbrs[j]->keypoint_angles.size())));
     }
     slot_use_[ref] = ++tick_;  // keep the reference resident while its neighbours are uploaded
+    std::vector<float> rot(nslots.size());
     float min_depth = 0.f, max_depth = 0.f;
-    StereoSearchConstraints(kf, &min_depth, &max_depth);  // PM.cc:184
+    bool on_device = false;
+    if (opt_.device_priors) {  // after SlotOf: an image upload into a slot clears its observations
+        std::vector<sdm::KeyFrame*> kfs(1, kf);
+        kfs.insert(kfs.end(), nbrs.begin(), nbrs.end());
+        std::vector<int> ks(1, ref);
+        ks.insert(ks.end(), nslots.begin(), nslots.end());
+        on_device = UploadObservations(kfs, ks) && sdm_search_priors(ctx_, 1, &ref, (int)nslots.size(), nslots.data(), rot.data(),
+                                                                     &min_depth, &max_depth) == SDM_OK;
+    }
+    if (!on_device) {
+        for (size_t j = 0; j < nbrs.size(); j++)
+            // PM.cc:170-179: median in-plane rotation over shared map points, 0 without covisibility
+            rot[j] = sdm_median_rot_in_plane(kf->map_point_ids.data(), kf->keypoint_angles.data(),
+                                             (int)std::min(kf->map_point_ids.size(), kf->keypoint_angles.size()),
+                                             nbrs[j]->map_point_ids.data(), nbrs[j]->keypoint_angles.data(),
+                                             (int)std::min(nbrs[j]->map_point_ids.size(), nbrs[j]->keypoint_angles.size()));
+        StereoSearchConstraints(kf, &min_depth, &max_depth);  // PM.cc:184
+    }
     if (sdm_recon(ctx_, 1, &ref, (int)nslots.size(), nslots.data(), rot.data(), &min_depth, &max_depth) != SDM_OK) {
         report("SemiDenseRecon");
         return;
@@ -724,27 +755,47 @@ void ProbabilityMapping::SemiDenseReconBlock(const std::vector<sdm::KeyFrame*>& 
     for (int j : plan.recv_kf) recv_slot.push_back(slot[j]);
     // per-reference constants: depth prior (PM.cc:184) and median in-plane rotations (PM.cc:170-179)
     const int n = opt_.covisN;
+    bool obs_ok = false;
+    if (opt_.device_priors && !refs.empty()) {  // every keyframe the pass reconstructs or reads, once
+        std::vector<char> in(n_all, 0);
+        std::vector<sdm::KeyFrame*> kfs;
+        std::vector<int> ks;
+        for (size_t a = 0; a < refs.size(); a++) {
+            in[refs[a]] = 1;
+            for (int j : nbrs[a]) in[j] = 1;
+        }
+        for (int i = 0; i < n_all; i++)
+            if (in[i]) {
+                kfs.push_back(all[i]);
+                ks.push_back(slot[i]);
+            }
+        obs_ok = UploadObservations(kfs, ks);
+    }
     auto run_recon = [&](bool boundary) {
         std::vector<int> r, ns;
-        std::vector<float> rot, mind, maxd;
         for (size_t a = 0; a < refs.size(); a++) {
             if ((is_boundary[refs[a]] != 0) != boundary) continue;
-            sdm::KeyFrame* kf = all[refs[a]];
             r.push_back(slot[refs[a]]);
-            float mn = 0.f, mx = 0.f;
-            StereoSearchConstraints(kf, &mn, &mx);
-            mind.push_back(mn);
-            maxd.push_back(mx);
-            for (int j : nbrs[a]) {
-                sdm::KeyFrame* k2 = all[j];
-                ns.push_back(slot[j]);
-                rot.push_back(sdm_median_rot_in_plane(
-                    kf->map_point_ids.data(), kf->keypoint_angles.data(),
-                    (int)std::min(kf->map_point_ids.size(), kf->keypoint_angles.size()), k2->map_point_ids.data(),
-                    k2->keypoint_angles.data(), (int)std::min(k2->map_point_ids.size(), k2->keypoint_angles.size())));
-            }
+            for (int j : nbrs[a]) ns.push_back(slot[j]);
         }
         if (r.empty()) return true;
+        std::vector<float> rot(ns.size()), mind(r.size()), maxd(r.size());
+        if (!obs_ok || sdm_search_priors(ctx_, (int)r.size(), r.data(), n, ns.data(), rot.data(), mind.data(), maxd.data()) != SDM_OK) {
+            size_t q = 0, p = 0;
+            for (size_t a = 0; a < refs.size(); a++) {
+                if ((is_boundary[refs[a]] != 0) != boundary) continue;
+                sdm::KeyFrame* kf = all[refs[a]];
+                StereoSearchConstraints(kf, &mind[q], &maxd[q]);
+                q++;
+                for (int j : nbrs[a]) {
+                    sdm::KeyFrame* k2 = all[j];
+                    rot[p++] = sdm_median_rot_in_plane(
+                        kf->map_point_ids.data(), kf->keypoint_angles.data(),
+                        (int)std::min(kf->map_point_ids.size(), kf->keypoint_angles.size()), k2->map_point_ids.data(),
+                        k2->keypoint_angles.data(), (int)std::min(k2->map_point_ids.size(), k2->keypoint_angles.size()));
+                }
+            }
+        }
         if (sdm_recon(ctx_, (int)r.size(), r.data(), n, ns.data(), rot.data(), mind.data(), maxd.data()) != SDM_OK) {
             report("SemiDenseReconBlock");
             return false;

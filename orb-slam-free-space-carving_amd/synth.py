@@ -195,6 +195,46 @@ class Scene:
             d += 1
         return out
 
+    # -- ORB observations --------------------------------------------------------------------------
+    def observations(self, k, n_points, seed, no_angle=0.05, extra_keypoints=0.3):
+        """Keyframe k's ORB observations as sdm::KeyFrame carries them: (map_point_ids int32, angles float32 degrees,
+        depths float32).  n_points map points with global ids 0..n_points-1 lie on the scene's plane(s) (a quarter on the
+        strip when the scene has one), drawn from `seed` alone, so every keyframe of the scene sees the same points.
+        Each becomes a keypoint of keyframe k; a point that does not project into the image becomes a keypoint with
+        id -1.  About extra_keypoints * n_points further keypoints carry no map point.  A keypoint's angle is its point's
+        base angle minus the keyframe's roll, mod 360 -- so angle(nbr) - angle(ref) is rot_deg(ref, nbr) up to wrap-around
+        -- and a fraction no_angle of them is -1.  depths: camera-frame z of the points keyframe k observes, in keypoint
+        order (GetAllPointDepths()).  Keypoints are shuffled per keyframe."""
+        c = self.cam
+        g = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(self.seed) & 0xFFFFFFFF])
+        half_x = 0.55 * c["W"] / c["fx"] * self.z0
+        half_y = 0.55 * c["H"] / c["fy"] * self.z0
+        X = g.uniform(-half_x, half_x, n_points)
+        Y = g.uniform(-half_y, half_y, n_points)
+        Z = self.z0 + self.alpha * X + self.beta * Y
+        if self.strip:
+            on = g.uniform(0, 1, n_points) < 0.25
+            X = np.where(on, g.uniform(self.strip_x0, self.strip_x1, n_points), X)
+            Z = np.where(on, self.strip_z, self.z0 + self.alpha * X + self.beta * Y)
+        base = g.uniform(0.0, 360.0, n_points)
+        Rwc, C = self.pose(k)
+        Pc = (np.stack([X, Y, Z], axis=1) - C) @ Rwc  # Rcw (P - C), row vectors
+        z = Pc[:, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = c["fx"] * Pc[:, 0] / z + c["cx"]
+            v = c["fy"] * Pc[:, 1] / z + c["cy"]
+        seen = (z > 0) & (u >= 0) & (u <= c["W"] - 1) & (v >= 0) & (v <= c["H"] - 1)
+        gk = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(self.seed) & 0xFFFFFFFF, int(k) + 1])
+        n_extra = int(extra_keypoints * n_points)
+        ids = np.concatenate([np.where(seen, np.arange(n_points), -1), np.full(n_extra, -1)]).astype(np.int32)
+        ang = np.concatenate([np.mod(base - self.roll(k), 360.0), gk.uniform(0.0, 360.0, n_extra)]).astype(np.float32)
+        ang = np.where(ang >= np.float32(360.0), np.float32(0.0), ang)  # (a float rounded up to 360)
+        ang[gk.uniform(0, 1, len(ang)) < no_angle] = -1.0
+        dep = np.concatenate([np.where(seen, z, 0.0), np.zeros(n_extra)]).astype(np.float32)
+        order = gk.permutation(len(ids))
+        ids, ang, dep = ids[order], ang[order], dep[order]
+        return ids, ang.astype(np.float32), dep[ids >= 0]
+
     def depth_prior(self, spread=0.1):
         """(min_depth, max_depth) exactly as StereoSearchConstraints names them (PM.cc:381-382):
         inverse depths 1/(mu-2s), 1/(mu+2s) with mu = Z0, s = spread*Z0 (App. D: 0.1; the ORB depths of a real keyframe
