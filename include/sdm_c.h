@@ -156,10 +156,11 @@ int sdm_recon(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n, const int *n
  *
  * A slot holds its keyframe's observations as sdm::KeyFrame carries them: map_point_ids[n_kp] (< 0 = no map point),
  * angles[n_kp] (mvKeysUn[i].angle, degrees, < 0 = no angle), depths[n_depths] (GetAllPointDepths()).  Only entries with
- * id >= 0 && angle >= 0 are kept, sorted by id on the device.  Order: upload the slot's image FIRST -- every image upload
+ * id >= 0 && angle >= 0 are kept for the priors, sorted by id on the device; beside them the sorted id >= 0 list whatever
+ * the angle, for the covisibility weights below.  Order: upload the slot's image FIRST -- every image upload
  * into a slot (sdm_upload_keyframe, sdm_upload_image*, the batch and device variants) marks its observations absent.
- * Memory: nothing until the first observation upload; then 12 * SDM_MAX_OBSERVATIONS + 8 bytes per slot
- * (96 KiB; 6 MiB for 64 slots) plus staging buffers that grow with the largest call.
+ * Memory: nothing until the first observation upload; then 16 * SDM_MAX_OBSERVATIONS + 12 bytes per slot
+ * (128 KiB; 8 MiB for 64 slots) plus staging buffers that grow with the largest call.
  *
  * Refused with SDM_EINVAL, that slot's observations left absent and the batch's other keyframes stored: n_kp or n_depths
  * above SDM_MAX_OBSERVATIONS, a non-negative id that appears twice (the host helper would emit the cross product; the
@@ -181,6 +182,46 @@ int sdm_search_priors(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n, cons
                       float *min_depth, float *max_depth);
 /* sdm_search_priors + sdm_recon: the same maps as sdm_recon fed the host helpers' values */
 int sdm_recon_observed(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n, const int *nbr_slots);
+
+/* ---- covisible neighbours from the same observations, on the device -----------------------------
+ * What SemiDenseRecon does first (PM.cc:151-160): take the first n usable keyframes of the reference's covisibility
+ * order.  ref_slots[n_ref] are the references; cand_slots[n_cand] the keyframes the caller considers usable (PM.cc:156-157:
+ * not bad, Mapped()).  All of them must hold observations.
+ *
+ * Weight w(r, c): the number of distinct map-point ids >= 0 uploaded for both slots; the angle is not looked at
+ * (KeyFrame::UpdateConnections, KeyFrame.cc:302-320, counts every map point of the keyframe).  A candidate whose slot is
+ * the reference's has weight 0 and is never selected (KeyFrame.cc:316).
+ * Connected list of r (KeyFrame.cc:326-361): the candidates with w >= min_weight, by w descending; equal weights by
+ * position in cand_slots, ascending.  If none reaches min_weight but the largest weight is >= 1, the list is the one
+ * candidate with the largest weight, the earliest position among equals (KeyFrame.cc:348-352).  If every weight is 0 the
+ * list is empty (KeyFrame.cc:323).  SDM_COVIS_MIN_WEIGHT is the reference's th.
+ * The tie rule is a normative choice: the reference orders equal weights by KeyFrame pointer value, which no caller can
+ * reproduce; list position is the deterministic stand-in.
+ * Neighbours: the first n entries of the connected list.  counts[r] = min(n, its length); unused entries of nbr_slots are
+ * -1, of nbr_weights 0.
+ *
+ * SDM_ESTATE for a reference or candidate slot without observations.  SDM_EINVAL for a null pointer, n outside
+ * [1, max_neighbours], n_cand < 1, a slot out of range, a slot twice in cand_slots or twice in ref_slots, min_weight < 1.
+ * A reference may also be a candidate.  A refused call changes nothing, the output arrays included.  One copy in, two
+ * launches (one for sdm_covisibility), one copy out, one stream synchronise: the host needs the table before the search
+ * can be set up. */
+#define SDM_COVIS_MIN_WEIGHT 15                     /* KeyFrame.cc:330 */
+
+/* weights[n_ref][n_cand] (host), row-major: shared map points of every (reference, candidate) pair */
+int sdm_covisibility(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n_cand, const int *cand_slots, int *weights);
+
+/* nbr_slots[n_ref][n] (-1 padded), nbr_weights[n_ref][n] or NULL, counts[n_ref] or NULL: host arrays */
+int sdm_covisible_neighbours(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n_cand, const int *cand_slots,
+                             int n, int min_weight, int *nbr_slots, int *nbr_weights, int *counts);
+
+/* PM.cc:151-231 for a batch: choose the neighbours, derive the priors, reconstruct (sdm_covisible_neighbours, then
+ * sdm_recon_observed on the references that have n neighbours).
+ * done[r] = 1 if reference r had n neighbours and was reconstructed.
+ * done[r] = 0 if it had fewer: PM.cc:160 skips such a keyframe.  Its slot is left exactly as it was.
+ * nbr_slots_out [n_ref][n] may be NULL.  A refusal of sdm_recon_observed (a reference without an image or without point
+ * depths) is returned as it is, with done and nbr_slots_out unwritten. */
+int sdm_recon_covisible(sdm_ctx *ctx, int n_ref, const int *ref_slots, int n_cand, const int *cand_slots,
+                        int n, int min_weight, int *nbr_slots_out, unsigned char *done);
 
 /* ---- InterKeyFrameDepthChecking, PM.h:91 / PM.cc:628-799 -------------------------------------- */
 /* Reads the neighbours' current {rho,sigma}; writes the checked rho of each reference keyframe to

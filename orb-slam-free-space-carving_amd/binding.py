@@ -85,6 +85,9 @@ SYMBOLS = [
                                                 C.POINTER(C.c_void_p)]),
     ("sdm_search_priors", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, _f32p, _f32p, _f32p]),
     ("sdm_recon_observed", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip]),
+    ("sdm_covisibility", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, _ip]),
+    ("sdm_covisible_neighbours", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip, _ip]),
+    ("sdm_recon_covisible", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, _ip, _u8p]),
     ("sdm_inter_check", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int]),
     ("sdm_pointset", C.c_int, [_ctx, C.c_int, _ip, C.c_int]),
     ("sdm_inter_check_pointset", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int]),
@@ -416,6 +419,44 @@ class Engine:
         nbrs = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(len(refs), -1)
         self._check(self.lib.sdm_recon_observed(self.ctx, len(refs), refs.ctypes.data_as(_ip), nbrs.shape[1],
                                                 nbrs.ctypes.data_as(_ip)))
+
+    # -- covisible neighbours from the same observations (sdm_covisibility, sdm_covisible_neighbours) -----------------
+    def covisibility(self, refs, cands):
+        """weights [n_ref, n_cand] int32: map points (ids >= 0) every (reference, candidate) pair shares"""
+        refs = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        cands = np.ascontiguousarray(cands, dtype=np.int32).reshape(-1)
+        w = np.zeros((len(refs), len(cands)), np.int32)
+        self._check(self.lib.sdm_covisibility(self.ctx, len(refs), refs.ctypes.data_as(_ip), len(cands),
+                                              cands.ctypes.data_as(_ip), w.ctypes.data_as(_ip)))
+        return w
+
+    def covisible_neighbours(self, refs, cands, n, min_weight=15):
+        """(nbrs [n_ref, n] -1 padded, weights [n_ref, n] 0 padded, counts [n_ref]) int32: the first n entries of every
+        reference's connected list (KeyFrame.cc:326-361; equal weights in cands order)"""
+        refs = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        cands = np.ascontiguousarray(cands, dtype=np.int32).reshape(-1)
+        n = int(n)
+        nbrs = np.full((len(refs), max(n, 0)), -1, np.int32)
+        w = np.zeros((len(refs), max(n, 0)), np.int32)
+        cnt = np.zeros(len(refs), np.int32)
+        self._check(self.lib.sdm_covisible_neighbours(self.ctx, len(refs), refs.ctypes.data_as(_ip), len(cands),
+                                                      cands.ctypes.data_as(_ip), n, int(min_weight),
+                                                      nbrs.ctypes.data_as(_ip), w.ctypes.data_as(_ip),
+                                                      cnt.ctypes.data_as(_ip)))
+        return nbrs, w, cnt
+
+    def recon_covisible(self, refs, cands, n, min_weight=15):
+        """(nbrs [n_ref, n], done [n_ref] bool): covisible_neighbours, then recon_observed on the references that have n
+        neighbours; the others are skipped as PM.cc:160 skips them"""
+        refs = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        cands = np.ascontiguousarray(cands, dtype=np.int32).reshape(-1)
+        n = int(n)
+        nbrs = np.full((len(refs), max(n, 0)), -1, np.int32)
+        done = np.zeros(len(refs), np.uint8)
+        self._check(self.lib.sdm_recon_covisible(self.ctx, len(refs), refs.ctypes.data_as(_ip), len(cands),
+                                                 cands.ctypes.data_as(_ip), n, int(min_weight),
+                                                 nbrs.ctypes.data_as(_ip), done.ctypes.data_as(_u8p)))
+        return nbrs, done.astype(bool)
 
     def intra_check(self, refs):
         r, rp = _i32(np.asarray(refs).reshape(-1))

@@ -29,6 +29,7 @@
 #include "sdm_kernels.h"
 #include "sdm_extract.h"
 #include "sdm_priors.h"
+#include "sdm_covis.h"
 
 using namespace sdm;
 
@@ -246,6 +247,8 @@ struct sdm_ctx {
     size_t obs_dev_bytes = 0, obs_host_bytes = 0;
     unsigned char *d_pri = nullptr, *h_pri = nullptr;  // sdm_search_priors: slot tables in, priors out
     size_t pri_dev_bytes = 0, pri_host_bytes = 0;
+    unsigned char *d_cov = nullptr, *h_cov = nullptr;  // sdm_covisib*: slot lists in, weight matrix, neighbour lists out
+    size_t cov_dev_bytes = 0, cov_host_bytes = 0;
 };
 
 namespace {
@@ -1097,6 +1100,10 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipHostFree(c->h_obs_stage);
     (void)hipFree(c->d_pri);
     (void)hipHostFree(c->h_pri);
+    (void)hipFree(c->obs.cov_ids);
+    (void)hipFree(c->obs.cov_cnt);
+    (void)hipFree(c->d_cov);
+    (void)hipHostFree(c->h_cov);
     for (auto& sp : c->spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
@@ -2442,7 +2449,9 @@ static int obs_alloc(sdm_ctx* c)
     int rc;
     if ((!c->obs.ids && (rc = dev_alloc(&c->obs.ids, per))) || (!c->obs.ang && (rc = dev_alloc(&c->obs.ang, per))) ||
         (!c->obs.depth && (rc = dev_alloc(&c->obs.depth, per))) || (!c->obs.cnt && (rc = dev_alloc(&c->obs.cnt, (size_t)K))) ||
-        (!c->obs.nd && (rc = dev_alloc(&c->obs.nd, (size_t)K))))
+        (!c->obs.nd && (rc = dev_alloc(&c->obs.nd, (size_t)K))) ||
+        (!c->obs.cov_ids && (rc = dev_alloc(&c->obs.cov_ids, per))) ||
+        (!c->obs.cov_cnt && (rc = dev_alloc(&c->obs.cov_cnt, (size_t)K))))
         return rc;
     // the sort holds a keyframe's ids and angles in LDS: 64 KB at the cap
     HIP_TRY(hipFuncSetAttribute((const void*)k_obs_ingest, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2629,6 +2638,140 @@ int sdm_recon_observed(sdm_ctx* c, int n_ref, const int* ref_slots, int n, const
         return sdm_recon(c, n_ref, ref_slots, n, nbr_slots, rot.data(), mind.data(), maxd.data());
     } catch (const std::exception& e) {
         return fail(SDM_EHIP, std::string("recon observed: ") + e.what());
+    }
+}
+
+// ---- covisible neighbours from resident ORB observations (sdm_covis.h) ---------------------------------------------------
+// every check of the three entry points; nothing is touched before it passes
+static int covis_check(sdm_ctx* c, int n_ref, const int* ref_slots, int n_cand, const int* cand_slots)
+{
+    if (!c) return fail(SDM_EINVAL, "null context");
+    if (n_ref <= 0 || !ref_slots) return fail(SDM_EINVAL, "n_ref <= 0 or null ref_slots");
+    if (n_cand < 1 || !cand_slots) return fail(SDM_EINVAL, "n_cand < 1 or null cand_slots");
+    int rc;
+    for (int pass = 0; pass < 2; pass++) {
+        const int m = pass ? n_cand : n_ref;
+        const int* slots = pass ? cand_slots : ref_slots;
+        std::vector<char> seen((size_t)c->cfg.max_keyframes, 0);
+        for (int i = 0; i < m; i++) {
+            if ((rc = check_slot(c, slots[i], false))) return rc;
+            if (seen[slots[i]]) return fail(SDM_EINVAL, pass ? "a slot twice in cand_slots" : "a slot twice in ref_slots");
+            seen[slots[i]] = 1;
+        }
+    }
+    for (int i = 0; i < n_ref + n_cand; i++) {
+        const int s = i < n_ref ? ref_slots[i] : cand_slots[i - n_ref];
+        if (c->has_obs.empty() || !c->has_obs[s]) return fail(SDM_ESTATE, "slot " + std::to_string(s) + " has no observations");
+    }
+    return SDM_OK;
+}
+
+// the weight matrix (n == 0) or the neighbour lists of n_ref references: one copy in, one or two launches, one copy out,
+// one stream synchronise.  Host outputs may be null.
+static int covis_impl(sdm_ctx* c, int n_ref, const int* ref_slots, int n_cand, const int* cand_slots, int n, int min_weight,
+                      int* weights, int* nbr_slots, int* nbr_weights, int* counts)
+{
+    int rc = covis_check(c, n_ref, ref_slots, n_cand, cand_slots);
+    if (rc) return rc;
+    if (n > 0) {
+        if (n > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n out of [1, max_neighbours]");
+        if (min_weight < 1) return fail(SDM_EINVAL, "min_weight < 1");
+    }
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t nw = (size_t)n_ref * n_cand, np = (size_t)n_ref * n;
+    const size_t in_bytes = ext_align(sizeof(int) * ((size_t)n_ref + n_cand));
+    const size_t w_bytes = ext_align(sizeof(int) * nw);
+    const size_t out_words = 2 * np + (size_t)n_ref;
+    const size_t total = in_bytes + w_bytes + sizeof(int) * out_words;
+    if ((rc = ext_grow_host(&c->h_cov, &c->cov_host_bytes, total)) || (rc = ext_grow_dev(&c->d_cov, &c->cov_dev_bytes, total)))
+        return rc;
+    memcpy(c->h_cov, ref_slots, sizeof(int) * n_ref);
+    memcpy(c->h_cov + sizeof(int) * n_ref, cand_slots, sizeof(int) * n_cand);
+    int max_kp = 1;
+    for (int r = 0; r < n_ref; r++) max_kp = std::max(max_kp, c->obs_kp[ref_slots[r]]);
+    CovisArgs a;
+    a.st = c->obs;
+    a.refs = (const int*)c->d_cov;
+    a.cands = a.refs + n_ref;
+    a.weights = (int*)(c->d_cov + in_bytes);
+    a.nbr_slots = (int*)(c->d_cov + in_bytes + w_bytes);
+    a.nbr_weights = a.nbr_slots + np;
+    a.counts = a.nbr_weights + np;
+    a.n_ref = n_ref;
+    a.n_cand = n_cand;
+    a.n = n;
+    a.min_weight = min_weight;
+    // about 1024 workgroups (four per CU) once the call has that many pairs; never fewer than one candidate per wave,
+    // never more than 64 per workgroup
+    const long long want = ((long long)nw + 1023) / 1024;
+    a.per_block = (int)std::min<long long>(64, std::max<long long>(OBS_WAVES, (want + OBS_WAVES - 1) / OBS_WAVES * OBS_WAVES));
+    const unsigned gy = (unsigned)((n_cand + a.per_block - 1) / a.per_block);
+    if (gy > 65535u) return fail(SDM_EINVAL, "n_cand too large");
+    HIP_TRY(hipMemcpyAsync(c->d_cov, c->h_cov, sizeof(int) * ((size_t)n_ref + n_cand), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_covis_weights, dim3((unsigned)n_ref, gy), dim3(OBS_BLOCK), sizeof(int) * max_kp, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (n > 0) {
+        hipLaunchKernelGGL(k_covis_select, dim3((unsigned)n_ref), dim3(OBS_BLOCK), 0, c->stream, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_cov + in_bytes + w_bytes, a.nbr_slots, sizeof(int) * out_words, hipMemcpyDeviceToHost,
+                               c->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(c->h_cov + in_bytes, a.weights, sizeof(int) * nw, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (weights) memcpy(weights, c->h_cov + in_bytes, sizeof(int) * nw);
+    const int* h_out = (const int*)(c->h_cov + in_bytes + w_bytes);
+    if (nbr_slots) memcpy(nbr_slots, h_out, sizeof(int) * np);
+    if (nbr_weights) memcpy(nbr_weights, h_out + np, sizeof(int) * np);
+    if (counts) memcpy(counts, h_out + 2 * np, sizeof(int) * n_ref);
+    return SDM_OK;
+}
+
+int sdm_covisibility(sdm_ctx* c, int n_ref, const int* ref_slots, int n_cand, const int* cand_slots, int* weights)
+{
+    try {
+        if (c && !weights) return fail(SDM_EINVAL, "null weights");
+        return covis_impl(c, n_ref, ref_slots, n_cand, cand_slots, 0, 0, weights, nullptr, nullptr, nullptr);
+    } catch (const std::exception& e) {
+        return fail(SDM_EHIP, std::string("covisibility: ") + e.what());
+    }
+}
+
+int sdm_covisible_neighbours(sdm_ctx* c, int n_ref, const int* ref_slots, int n_cand, const int* cand_slots, int n,
+                             int min_weight, int* nbr_slots, int* nbr_weights, int* counts)
+{
+    try {
+        if (c && !nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
+        if (c && n < 1) return fail(SDM_EINVAL, "n out of [1, max_neighbours]");
+        return covis_impl(c, n_ref, ref_slots, n_cand, cand_slots, n, min_weight, nullptr, nbr_slots, nbr_weights, counts);
+    } catch (const std::exception& e) {
+        return fail(SDM_EHIP, std::string("covisible neighbours: ") + e.what());
+    }
+}
+
+int sdm_recon_covisible(sdm_ctx* c, int n_ref, const int* ref_slots, int n_cand, const int* cand_slots, int n, int min_weight,
+                        int* nbr_slots_out, unsigned char* done)
+{
+    try {
+        if (c && !done) return fail(SDM_EINVAL, "null done");
+        if (c && n < 1) return fail(SDM_EINVAL, "n out of [1, max_neighbours]");
+        if (c && n_ref <= 0) return fail(SDM_EINVAL, "n_ref <= 0 or null ref_slots");
+        std::vector<int> nbrs((size_t)std::max(n_ref, 0) * n), counts((size_t)std::max(n_ref, 0));
+        int rc = covis_impl(c, n_ref, ref_slots, n_cand, cand_slots, n, min_weight, nullptr, nbrs.data(), nullptr, counts.data());
+        if (rc) return rc;
+        // PM.cc:160: a keyframe with fewer than n usable neighbours is skipped
+        std::vector<int> refs2, nbrs2;
+        for (int r = 0; r < n_ref; r++)
+            if (counts[r] == n) {
+                refs2.push_back(ref_slots[r]);
+                nbrs2.insert(nbrs2.end(), nbrs.begin() + (size_t)r * n, nbrs.begin() + (size_t)(r + 1) * n);
+            }
+        if (!refs2.empty() && (rc = sdm_recon_observed(c, (int)refs2.size(), refs2.data(), n, nbrs2.data()))) return rc;
+        for (int r = 0; r < n_ref; r++) done[r] = counts[r] == n;
+        if (nbr_slots_out) memcpy(nbr_slots_out, nbrs.data(), sizeof(int) * nbrs.size());
+        return SDM_OK;
+    } catch (const std::exception& e) {
+        return fail(SDM_EHIP, std::string("recon covisible: ") + e.what());
     }
 }
 

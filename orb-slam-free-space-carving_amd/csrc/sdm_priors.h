@@ -3,7 +3,7 @@
 //
 // A slot's observations are its keyframe's map-point id and keypoint angle per keypoint, and GetAllPointDepths().  At
 // upload only the entries that can ever contribute to GetRotInPlane are kept -- id >= 0 && angle >= 0, the host helper's
-// filter (PM.cc:467-484) -- sorted by id:
+// filter (PM.cc:467-484) -- sorted by id (beside them the sorted id >= 0 list whatever the angle, for sdm_covis.h):
 //   k_obs_ingest   one workgroup per keyframe: compact the id >= 0 entries into LDS, bitonic sort by id, flag a repeated
 //                  id and a non-finite angle, then compact the angle >= 0 entries to the slot's arrays; copy the depths
 // The priors of a call:
@@ -41,6 +41,8 @@ struct ObsStore {      // resident observations, OBS stride per slot
     int* cnt;          // [max_keyframes] kept entries
     int* nd;           // [max_keyframes] depths
     int cap;
+    int* cov_ids;      // [max_keyframes][cap] sorted, every id >= 0 whatever its angle (sdm_covis.h)
+    int* cov_cnt;      // [max_keyframes]
 };
 
 // order-preserving map of a float to a 32-bit unsigned key (-0 sorts just below +0) and back
@@ -132,8 +134,10 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_obs_ingest(const ObsItem* __restr
     // 3. a repeated id: the host helper would emit the cross product of its matches
     for (int i = 1 + (int)threadIdx.x; i < m; i += OBS_BLOCK)
         if (key[i] == key[i - 1]) atomicOr(&bad, OBS_BAD_DUPLICATE);
-    // 4. the angle >= 0 entries, still sorted, to the slot
     const long long base = (long long)it.slot * st.cap;
+    // ... and all of them, sorted, for the covisibility weights (KeyFrame::UpdateConnections does not look at the angle)
+    for (int i = (int)threadIdx.x; i < m; i += OBS_BLOCK) st.cov_ids[base + i] = (int)key[i];
+    // 4. the angle >= 0 entries, still sorted, to the slot
     int kept = 0;
     for (int i0 = 0; i0 < m; i0 += OBS_BLOCK) {
         const int i = i0 + (int)threadIdx.x;
@@ -151,6 +155,7 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_obs_ingest(const ObsItem* __restr
     if (threadIdx.x == 0) {
         st.cnt[it.slot] = kept;
         st.nd[it.slot] = it.n_depths;
+        st.cov_cnt[it.slot] = m;
         status[blockIdx.x] = bad;
     }
 }
