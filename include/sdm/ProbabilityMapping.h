@@ -189,6 +189,22 @@ public:
      * order; numbers through operator<<(double) like the reference.  Returns the number of points. */
     long AppendTranscriptEntry(sdm::KeyFrame* kf, int camIndex, int camIndexOriginal, std::ostream& out,
                                double max_sigma = 0.01);
+    /* The same entry in the transcript's visibility-list form, `new point: [x; y; z], KF_ind1, ..., KF_indN` -- what
+     * addKeyFrameInsertionEntry writes for ORB points seen from more than one keyframe
+     * (SFMTranscriptInterface_ORBSLAM.cpp:274-284) -- so that CARV carves along every (camera, point) ray:
+     *     new cam: [x; y; z] {
+     *     new point: [x; y; z], <camIndex>, <neighborCamIndex[j]>, ...
+     *     }
+     * The `new cam:` line and the point filter are AppendTranscriptEntry's.  A point's list is camIndex followed by
+     * neighborCamIndex[j] for every neighbors[j] that the inter-keyframe check's statement (PM.cc:677-755) counts for the
+     * point at the keyframe's current depth map, j ascending: the neighbours whose own depth map agrees with the point
+     * (sdm_extract_points_support over the keyframes' slots, after host-edited maps have been brought up to date).
+     * Returns the number of points; -1, with a message on cerr, when kf has no point set, a neighbour has no depth map
+     * (semidense_flag_), the two vectors differ in size or are empty, or the engine refuses the call (more neighbours
+     * than the context was sized for, Options::covisN). */
+    long AppendTranscriptEntryWithVisibility(sdm::KeyFrame* kf, int camIndex, const std::vector<sdm::KeyFrame*>& neighbors,
+                                             const std::vector<int>& neighborCamIndex, std::ostream& out,
+                                             double max_sigma = 0.01);
     bool ok() const { return ctx_ != nullptr; }
 
     /* ---- device-slot cache contract (keyframes are cached by address) --------------------------------------

@@ -285,6 +285,34 @@ typedef struct {
  * fields, which is also what crosses the link for a host destination. */
 int sdm_extract_points(sdm_ctx *ctx, int n, const int *slots, int source, double max_sigma, double min_rho,
                        sdm_point_buffers *out, long long *offsets);
+/* sdm_extract_points plus, per point, which neighbour keyframes confirm it: the point's visibility list (the
+ * `KF_ind1, ..., KF_indN` of the transcript's `new point:` line).  Same points, order, offsets and fields as
+ * sdm_extract_points for the same arguments; in addition support[p], p < total, is a 64-bit word whose bit j is set iff
+ * the statement of PM.cc:677-755, run for neighbour nbr_slots[i * n_nbr + j] of the point's slot slots[i] on the state
+ * at the time of the call, counts that neighbour (`nj >= 1`, PM.cc:755) -- the set behind the count
+ * InterKeyFrameDepthChecking compares with lambdaN.
+ *   - the point's rho in that statement is the rho of its slot's DEPTH MAP (the plane sdm_inter_check reads), whatever
+ *     `source` selects for the filter; the neighbour's {rho, sigma} are its current depth map; the arithmetic is
+ *     sdm_inter_check's (bit-identical decisions, its guard and exact fallback included);
+ *   - the word is 0 for a pixel outside the 2-px inset (PM.cc:659-660) and for a pixel whose depth-map rho is skipped by
+ *     PM.cc:662 ((double)rho < 1e-6); bits >= n_nbr are 0; lambdaN plays no part.
+ * Consequences: after sdm_inter_check(commit = 0) on the same neighbour table the words reproduce the check's own
+ * decisions -- for every inset pixel not skipped by PM.cc:662, popcount < lambdaN => checked rho == 0, and
+ * checked rho != 0 => popcount >= lambdaN.  After commit = 1 the words are evaluated at the committed rho.
+ * support[out->capacity] follows out->on_device (8-byte aligned there) and is a separate argument: sdm_point_buffers
+ * keeps its layout.  All four field pointers may be NULL.
+ * Errors: those of sdm_extract_points (total > capacity: offsets filled, nothing written) and of sdm_inter_check's
+ * neighbour table: SDM_EINVAL for NULL support / nbr_slots, n_nbr < 1 or > max_neighbours, a neighbour slot out of
+ * range (a repeated neighbour is accepted, as there); SDM_ESTATE for a slot without an uploaded keyframe or a neighbour
+ * without a depth map.
+ * Changes no plane, flag or list.  Staging the pair tables counts in sdm_stats::table_stagings as for any compute call,
+ * and the staged set is shared with an sdm_inter_check over the same lists.
+ * Cost on top of sdm_extract_points: one lane per point runs K4's per-neighbour statement n_nbr times (a subset of
+ * sdm_inter_check's work on a subset of its pixels) and 8 B per point are written (and cross the link for a host
+ * destination); 4 B per point of staged pixel codes when `pixel` is NULL. */
+int sdm_extract_points_support(sdm_ctx *ctx, int n, const int *slots, int n_nbr, const int *nbr_slots /*[n][n_nbr]*/,
+                               int source, double max_sigma, double min_rho, sdm_point_buffers *out,
+                               unsigned long long *support /*[out->capacity]*/, long long *offsets);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -97,6 +97,8 @@ SYMBOLS = [
     ("sdm_download_pointset", C.c_int, [_ctx, C.c_int, _f32p]),
     ("sdm_extract_points", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.POINTER(PointBuffers),
                                      C.POINTER(C.c_longlong)]),
+    ("sdm_extract_points_support", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double,
+                                             C.POINTER(PointBuffers), C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -513,6 +515,21 @@ class Engine:
         out: {field: preallocated array} -- NumPy (pageable, or pinned from host_alloc) or torch device tensors (all of
         one kind); the returned arrays are views of their first `total` points.  Too small: SdmError with .offsets.
         Without out the buffers are sized by extract_bound: the list length of the slots walked by list, W*H of the others."""
+        return self._extract(slots, None, source, max_sigma, min_rho, fields, out)
+
+    def extract_points_support(self, slots, nbrs, source=1, max_sigma=0.01, min_rho=1e-6, fields=("xyz",), out=None):
+        """extract_points plus "support" (uint64[m], sdm_extract_points_support): bit j of a point's word is set iff
+        neighbour nbrs[i][j] of its slot slots[i] is counted by the inter-keyframe check's statement (PM.cc:677-755) at the
+        slot's depth-map rho -- the point's visibility list.  fields may be empty; out may carry a preallocated "support"
+        (uint64 array, or a torch device tensor of 8-byte elements) under extract_points' rules."""
+        sl = np.asarray(slots, dtype=np.int32).reshape(-1)
+        nb = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(len(sl), -1)
+        return self._extract(sl, nb, source, max_sigma, min_rho, fields, out)
+
+    def _extract(self, slots, nbrs, source, max_sigma, min_rho, fields, out):
+        known = dict(POINT_FIELDS)
+        if nbrs is not None:
+            known["support"] = (np.uint64, 1)
         sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
         n = len(sl)
         if out is None:
@@ -522,12 +539,21 @@ class Engine:
             cap = max(self.extract_bound(sl, source, min_rho), 1)
             out = {f: np.empty((cap, POINT_FIELDS[f][1]) if POINT_FIELDS[f][1] > 1 else (cap,), POINT_FIELDS[f][0])
                    for f in fields}
+            if nbrs is not None:
+                out["support"] = np.empty(cap, np.uint64)
+        elif nbrs is not None and "support" not in out:
+            out = dict(out)
+            kind_dev = any(not isinstance(a, np.ndarray) for a in out.values())
+            if kind_dev:
+                raise ValueError('device destinations need a "support" tensor in out')
+            caps = [a.size // POINT_FIELDS[f][1] for f, a in out.items() if f in POINT_FIELDS]
+            out["support"] = np.empty(min(caps) if caps else max(self.extract_bound(sl, source, min_rho), 1), np.uint64)
         pb = PointBuffers()
-        cap, kinds = None, set()
+        cap, kinds, sup_ptr = None, set(), None
         for f, a in out.items():
-            if f not in POINT_FIELDS:
+            if f not in known:
                 raise ValueError("unknown point field %r" % (f,))
-            dt, per = POINT_FIELDS[f]
+            dt, per = known[f]
             if isinstance(a, np.ndarray):
                 if a.dtype != dt or not a.flags.c_contiguous or a.size % per:
                     raise ValueError("%s: need a C-contiguous %s array of [m, %d]" % (f, np.dtype(dt).name, per))
@@ -540,24 +566,34 @@ class Engine:
                     raise ValueError("%s: tensor on device %d, engine on device %d" % (f, a.get_device(), self.device))
                 kinds.add("device")
                 ptr, m = a.data_ptr(), a.numel() // per
-                align = 8 if f == "rho_sigma" else np.dtype(dt).itemsize  # (the kernel stores {rho, sigma} as one float2)
+                # (the kernels store {rho, sigma} as one float2 and a support word as one 8-byte value)
+                align = 8 if f in ("rho_sigma", "support") else np.dtype(dt).itemsize
                 if ptr % align:
                     raise ValueError("%s: device tensor address not %d-byte aligned" % (f, align))
-            setattr(pb, f, ptr)
+            if f == "support":
+                sup_ptr = ptr
+            else:
+                setattr(pb, f, ptr)
             cap = m if cap is None else min(cap, m)
         if len(kinds) > 1:
             raise ValueError("out mixes host arrays and device tensors")
         pb.capacity = cap if cap is not None else 0
         pb.on_device = 1 if kinds == {"device"} else 0
         offs = np.zeros(n + 1, np.int64)
-        rc = self.lib.sdm_extract_points(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma), float(min_rho),
-                                         C.byref(pb), offs.ctypes.data_as(C.POINTER(C.c_longlong)))
+        offp = offs.ctypes.data_as(C.POINTER(C.c_longlong))
+        if nbrs is None:
+            rc = self.lib.sdm_extract_points(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma), float(min_rho),
+                                             C.byref(pb), offp)
+        else:
+            rc = self.lib.sdm_extract_points_support(self.ctx, n, sl.ctypes.data_as(_ip), nbrs.shape[1], nbrs.ctypes.data_as(_ip),
+                                                     int(source), float(max_sigma), float(min_rho), C.byref(pb),
+                                                     C.cast(sup_ptr, C.POINTER(C.c_ulonglong)), offp)
         if rc:
             e = SdmError(rc, self.lib.sdm_last_error().decode())
             e.offsets = offs
             raise e
         total = int(offs[n])
-        res = {f: a[:total] if POINT_FIELDS[f][1] == 1 else a.reshape(-1, POINT_FIELDS[f][1])[:total] for f, a in out.items()}
+        res = {f: a[:total] if known[f][1] == 1 else a.reshape(-1, known[f][1])[:total] for f, a in out.items()}
         res["offsets"] = offs
         return res
 

@@ -28,6 +28,7 @@
 #include "sdm_c.h"
 #include "sdm_kernels.h"
 #include "sdm_extract.h"
+#include "sdm_support.h"
 #include "sdm_priors.h"
 #include "sdm_covis.h"
 
@@ -593,7 +594,7 @@ struct StageTimer {
 // Stage the tables of a call (slot lists, per-reference offsets, search constants) and build
 // RefConst/PairConst on device.  need_consts: rot/mind/maxd matter (K1); otherwise any cached value is fine.
 int stage_tables(sdm_ctx* c, int n_ref, const int* ref_slots, int n, const int* nbr_slots, const float* rot,
-                 const float* mind, const float* maxd, bool need_consts = false)
+                 const float* mind, const float* maxd, bool need_consts = false, bool rebuild_stale = true)
 {
     if (n_ref <= 0 || !ref_slots) return fail(SDM_EINVAL, "n_ref <= 0 or null ref_slots");
     if (n_ref > c->cap_refs) return fail(SDM_EINVAL, "n_ref exceeds max_keyframes");
@@ -609,7 +610,7 @@ int stage_tables(sdm_ctx* c, int n_ref, const int* ref_slots, int n, const int* 
     }
     HIP_TRY(hipSetDevice(c->cfg.device));
     int rc;
-    {  // lists follow lambdaG (sdm_set_params); so do the gradient-gate bit planes K1's scan reads of the NEIGHBOURS
+    if (rebuild_stale) {  // lists follow lambdaG (sdm_set_params); so do the gradient-gate bit planes K1's scan reads of the NEIGHBOURS
         std::vector<int> stale;
         std::vector<char> seen((size_t)c->cfg.max_keyframes, 0);
         auto look = [&](int slot) {
@@ -2160,26 +2161,43 @@ int sdm_extract_bound(sdm_ctx* c, int n, const int* slots, int source, double mi
     return SDM_OK;
 }
 
-int sdm_extract_points(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
-                       sdm_point_buffers* out, long long* offsets)
+// sdm_extract_points (support == nullptr) and sdm_extract_points_support: the three extraction passes, then -- for the
+// second -- k_point_support over the compacted pixel codes (sdm_support.h)
+static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
+                        double min_rho, sdm_point_buffers* out, unsigned long long* support, long long* offsets)
 {
-    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
-    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity) return fail(SDM_EINVAL, "no output field requested");
     if (out->capacity < 0) return fail(SDM_EINVAL, "negative capacity");
     if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel) % 4 || (uintptr_t)out->rho_sigma % 8))
         return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel: 4 B; rho_sigma: 8 B)");
+    if (out->on_device && (uintptr_t)support % 8) return fail(SDM_EINVAL, "device buffer not aligned (support: 8 B)");
     std::vector<char> use_list;
     std::vector<int> count;
     int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
     if (rc) return rc;
     if (out->xyz && !c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
+    if (support) {  // sdm_inter_check's checks of the neighbour table (the slots themselves: ext_plan)
+        if (n_nbr < 1) return fail(SDM_EINVAL, "need at least one neighbour");
+        if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
+        for (size_t i = 0; i < (size_t)n * (size_t)n_nbr; i++) {
+            const int s = nbr_slots[i];
+            if (s < 0 || s >= c->cfg.max_keyframes) return fail(SDM_EINVAL, "slot out of range");
+            if (!c->has_depth[s])
+                return fail(SDM_ESTATE, "neighbour slot has no depth map (sdm_recon, sdm_upload_depth, an sdm_exchange_* "
+                                        "call or sdm_mark_depth_present must come first)");
+        }
+    }
     HIP_TRY(hipSetDevice(c->cfg.device));
+    // RefConst / PairConst of the call (the set an sdm_inter_check over the same lists staged serves this call too); the
+    // lists are left as they are: this call changes none
+    if (support && n > 0 && (rc = stage_tables(c, n, slots, n_nbr, nbr_slots, nullptr, nullptr, nullptr, false, false))) return rc;
 
     const size_t tab_b = ext_align(sizeof(ExtractSlot) * (size_t)std::max(n, 1));
     const size_t offs_b = ext_align(sizeof(unsigned long long) * (size_t)(n + 1));
-    if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, tab_b + offs_b))) return rc;
+    const size_t cut_b = support ? ext_align(sizeof(long long) * (size_t)(n + 1)) : 0;  // first workgroup per slot (k_point_support's block0)
+    if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, tab_b + offs_b + cut_b))) return rc;
     ExtractSlot* h_tab = reinterpret_cast<ExtractSlot*>(c->h_ext);
     unsigned long long* h_offs = reinterpret_cast<unsigned long long*>(c->h_ext + tab_b);
+    long long* h_cut = reinterpret_cast<long long*>(c->h_ext + tab_b + offs_b);
     long long nt = 0;
     for (int i = 0; i < n; i++) {
         ExtractSlot& d = h_tab[i];
@@ -2201,13 +2219,14 @@ int sdm_extract_points(sdm_ctx* c, int n, const int* slots, int source, double m
     const size_t cnt_b = ext_align(sizeof(unsigned) * (size_t)nt);
     const size_t toff_b = ext_align(sizeof(unsigned) * (size_t)(nt + 1));
     const size_t blk_b = ext_align(sizeof(unsigned long long) * (size_t)nb);
-    if ((rc = ext_grow_dev(&c->d_ext, &c->ext_bytes, tab_b + cnt_b + toff_b + 2 * blk_b + offs_b))) return rc;
+    if ((rc = ext_grow_dev(&c->d_ext, &c->ext_bytes, tab_b + cnt_b + toff_b + 2 * blk_b + offs_b + cut_b))) return rc;
     ExtractSlot* d_tab = reinterpret_cast<ExtractSlot*>(c->d_ext);
     unsigned* d_cnt = reinterpret_cast<unsigned*>(c->d_ext + tab_b);
     unsigned* d_toff = reinterpret_cast<unsigned*>(c->d_ext + tab_b + cnt_b);
     unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b);
     unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b + blk_b);
     unsigned long long* d_offs = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b + 2 * blk_b);
+    long long* d_cut = reinterpret_cast<long long*>(c->d_ext + tab_b + cnt_b + toff_b + 2 * blk_b + offs_b);
 
     ExtractIn in;
     in.tab = d_tab;
@@ -2236,39 +2255,81 @@ int sdm_extract_points(sdm_ctx* c, int n, const int* slots, int source, double m
                                                            std::to_string(total) + " points (offsets filled)");
     if (total == 0) return SDM_OK;
 
-    // where pass 3 writes: the caller's device buffers, or one staging region per requested field
+    // where pass 3 writes: the caller's device buffers, or one staging region per requested field (the pixel codes are
+    // staged for k_point_support when the caller did not ask for them)
     ExtractOut dst;
-    size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0;
-    if (out->on_device) {
-        dst.xyz = out->xyz;
-        dst.pixel = out->pixel;
-        dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
-        dst.intensity = out->intensity;
-    } else {
+    unsigned long long* d_sup = nullptr;
+    const bool stage_all = !out->on_device;
+    const bool stage_pix = support && !out->pixel;
+    size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, sup_off = 0;
+    {
         const size_t t = (size_t)total;
         size_t at = 0;
-        if (out->xyz) xyz_off = at, at += ext_align(12 * t);
-        if (out->pixel) pix_off = at, at += ext_align(4 * t);
-        if (out->rho_sigma) rs_off = at, at += ext_align(8 * t);
-        if (out->intensity) im_off = at, at += ext_align(t);
-        if ((rc = ext_grow_dev(&c->d_ext_stage, &c->ext_stage_bytes, at))) return rc;
-        unsigned char* b = c->d_ext_stage;
+        if (stage_all && out->xyz) xyz_off = at, at += ext_align(12 * t);
+        if ((stage_all && out->pixel) || stage_pix) pix_off = at, at += ext_align(4 * t);
+        if (stage_all && out->rho_sigma) rs_off = at, at += ext_align(8 * t);
+        if (stage_all && out->intensity) im_off = at, at += ext_align(t);
+        if (stage_all && support) sup_off = at, at += ext_align(8 * t);
+        if (at && (rc = ext_grow_dev(&c->d_ext_stage, &c->ext_stage_bytes, at))) return rc;
+    }
+    unsigned char* b = c->d_ext_stage;
+    if (out->on_device) {
+        dst.xyz = out->xyz;
+        dst.pixel = stage_pix ? reinterpret_cast<unsigned*>(b + pix_off) : out->pixel;
+        dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
+        dst.intensity = out->intensity;
+        d_sup = support;
+    } else {
         dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
-        dst.pixel = out->pixel ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
+        dst.pixel = (out->pixel || stage_pix) ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
         dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
         dst.intensity = out->intensity ? b + im_off : nullptr;
+        d_sup = support ? reinterpret_cast<unsigned long long*>(b + sup_off) : nullptr;
     }
     hipLaunchKernelGGL(k_extract_write, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_toff, d_boff, dst);
     HIP_TRY(hipGetLastError());
+    if (support) {
+        long long blocks = 0;
+        for (int i = 0; i < n; i++) {
+            h_cut[i] = blocks;
+            blocks += (offsets[i + 1] - offsets[i] + SUP_BLOCK - 1) / SUP_BLOCK;
+        }
+        h_cut[n] = blocks;
+        HIP_TRY(hipMemcpyAsync(d_cut, h_cut, sizeof(long long) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
+        const long long per = (1ll << 31) / SUP_BLOCK;  // work-items of one dispatch (for_ref_slices)
+        for (long long b0 = 0; b0 < blocks; b0 += per)
+            hipLaunchKernelGGL(k_point_support, dim3((unsigned)std::min(per, blocks - b0)), dim3(SUP_BLOCK), 0, c->stream,
+                               c->pool, c->P, c->d_refs, c->d_pairs, n, n_nbr, c->W, c->H, d_cut, b0, d_offs, dst.pixel, d_sup);
+        HIP_TRY(hipGetLastError());
+    }
     if (!out->on_device) {
         const size_t t = (size_t)total;
         if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, dst.xyz, 12 * t, hipMemcpyDeviceToHost, c->stream));
         if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, dst.pixel, 4 * t, hipMemcpyDeviceToHost, c->stream));
         if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, dst.rho_sigma, 8 * t, hipMemcpyDeviceToHost, c->stream));
         if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, dst.intensity, t, hipMemcpyDeviceToHost, c->stream));
+        if (support) HIP_TRY(hipMemcpyAsync(support, d_sup, 8 * t, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDM_OK;
+}
+
+int sdm_extract_points(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
+                       sdm_point_buffers* out, long long* offsets)
+{
+    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
+    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity) return fail(SDM_EINVAL, "no output field requested");
+    return extract_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, out, nullptr, offsets);
+}
+
+int sdm_extract_points_support(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
+                               double max_sigma, double min_rho, sdm_point_buffers* out, unsigned long long* support,
+                               long long* offsets)
+{
+    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
+    if (!support) return fail(SDM_EINVAL, "null support");
+    if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
+    return extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, out, support, offsets);
 }
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }

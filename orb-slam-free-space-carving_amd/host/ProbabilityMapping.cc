@@ -529,6 +529,73 @@ long ProbabilityMapping::AppendTranscriptEntry(sdm::KeyFrame* kf, int camIndex, 
     return n;
 }
 
+// SFMTranscriptInterface_ORBSLAM.cpp:274-284 (addKeyFrameInsertionEntry's visibility-list point lines): text form only.
+long ProbabilityMapping::AppendTranscriptEntryWithVisibility(sdm::KeyFrame* kf, int camIndex,
+                                                             const std::vector<sdm::KeyFrame*>& neighbors,
+                                                             const std::vector<int>& neighborCamIndex, std::ostream& out,
+                                                             double max_sigma)
+{
+    const char* where = "ProbabilityMapping::AppendTranscriptEntryWithVisibility: ";
+    if (!kf || kf->SemiDensePointSets_.empty()) return -1;
+    if (neighbors.empty() || neighbors.size() != neighborCamIndex.size()) {
+        std::cerr << where << neighbors.size() << " neighbours, " << neighborCamIndex.size() << " camera indices" << std::endl;
+        return -1;
+    }
+    for (size_t j = 0; j < neighbors.size(); j++)
+        if (!neighbors[j] || !neighbors[j]->semidense_flag_) {
+            std::cerr << where << "neighbour " << j << " has no depth map" << std::endl;
+            return -1;
+        }
+    const int ref = SlotOf(kf);
+    if (ref < 0) return -1;
+    slot_use_[ref] = ++tick_;  // keep the keyframe resident while its neighbours are uploaded
+    std::vector<int> nslots;
+    for (size_t j = 0; j < neighbors.size(); j++) {
+        const int s = SlotOf(neighbors[j]);
+        if (s < 0) return -1;
+        PushDepth(neighbors[j], s);
+        nslots.push_back(s);
+    }
+    PushDepth(kf, ref);
+    // the filter of AppendTranscriptEntry over the slot's depth map, which now equals kf->depth_map_ / depth_sigma_
+    long long bound = 0, offs[2] = {0, 0};
+    if (sdm_extract_bound(ctx_, 1, &ref, /*source = depth map*/ 0, 0.000001, &bound) != SDM_OK) {
+        report("AppendTranscriptEntryWithVisibility");
+        return -1;
+    }
+    std::vector<unsigned> pixel((size_t)std::max(bound, 1LL));
+    std::vector<unsigned long long> support(pixel.size());
+    sdm_point_buffers pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.pixel = pixel.data();
+    pb.capacity = (long long)pixel.size();
+    if (sdm_extract_points_support(ctx_, 1, &ref, (int)nslots.size(), nslots.data(), 0, max_sigma, 0.000001, &pb,
+                                   support.data(), offs) != SDM_OK) {
+        report("AppendTranscriptEntryWithVisibility");
+        return -1;
+    }
+    float Ow[3];  // as in AppendTranscriptEntry
+    for (int i = 0; i < 3; i++) {
+        float p0 = kf->Tcw[0 * 4 + i] * kf->Tcw[3];
+        float p1 = kf->Tcw[1 * 4 + i] * kf->Tcw[7];
+        float p2 = kf->Tcw[2 * 4 + i] * kf->Tcw[11];
+        Ow[i] = -((p0 + p1) + p2);
+    }
+    out << "new cam: [" << (double)Ow[0] << "; " << (double)Ow[1] << "; " << (double)Ow[2] << "] {" << std::endl;
+    for (long long p = 0; p < offs[1]; p++) {
+        const int x = (int)(pixel[p] & 0xffffu), y = (int)(pixel[p] >> 16);
+        out << "new point: [" << (double)kf->SemiDensePointSets_.at(y, 3 * x) << "; "
+            << (double)kf->SemiDensePointSets_.at(y, 3 * x + 1) << "; "
+            << (double)kf->SemiDensePointSets_.at(y, 3 * x + 2) << "]"
+            << ", " << camIndex;
+        for (size_t j = 0; j < neighbors.size(); j++)
+            if ((support[p] >> j) & 1ull) out << ", " << neighborCamIndex[j];
+        out << std::endl;
+    }
+    out << "}" << std::endl;
+    return (long)offs[1];
+}
+
 // ---- multi-GPU block driver -----------------------------------------------------------------
 bool ProbabilityMapping::InitSharding(const unsigned char* comm_id, int world, int rank)
 {
