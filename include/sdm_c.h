@@ -313,6 +313,56 @@ int sdm_extract_points(sdm_ctx *ctx, int n, const int *slots, int source, double
 int sdm_extract_points_support(sdm_ctx *ctx, int n, const int *slots, int n_nbr, const int *nbr_slots /*[n][n_nbr]*/,
                                int source, double max_sigma, double min_rho, sdm_point_buffers *out,
                                unsigned long long *support /*[out->capacity]*/, long long *offsets);
+/* sdm_extract_points merged to one point per voxel ACROSS the slots of the call: every keyframe re-observes the surface
+ * its neighbours have mapped, so the plain cloud holds a surface patch once per keyframe that sees it.  Nothing in the
+ * reference merges the cloud; the semantics below are this library's and are a pure function of the arguments and the
+ * planes (tests/voxel_np.py restates them in NumPy).
+ *   - Plain cloud: g = 0 .. T-1 are the points sdm_extract_points returns for the same (slots, source, max_sigma,
+ *     min_rho), in its order; xyz is the point-set plane as stored, sigma the depth map's.
+ *   - Cell: inv = 1.0f / voxel_size (one float division, on the host); c_k = floorf(xyz_k * inv), one float multiply
+ *     per coordinate, never fused.  A point is MERGEABLE iff -2^20 <= c_k < 2^20 for all three k (a NaN or +-Inf
+ *     coordinate fails); its voxel is the integer triple.  An unmergeable point is always kept, with multiplicity 1,
+ *     and is its own representative.
+ *   - Winner: among the mergeable points of one voxel the kept one minimises (key(sigma), g) lexicographically, where
+ *     with u = the bits of sigma, key(sigma) = u ^ ((u >> 31) ? 0xFFFFFFFF : 0x80000000) -- the order-preserving map
+ *     of the float order onto unsigned integers, total on bit patterns: -0 < +0, and a NaN has a defined place (above
+ *     +Inf with the sign bit clear, below -Inf with it set).  So: the smallest sigma wins; ties go to the slot listed
+ *     earlier in the call, then to raster order.
+ *   - Output: the kept points in plain order.  The fields of `out` carry the kept point's own values (nothing is
+ *     averaged); offsets[i], i < n, is the first kept point of slot i, offsets[n] the kept total M.
+ *     multiplicity[k] = plain points in kept point k's voxel; source_index[k] = its g (strictly increasing);
+ *     representative[g] = the k of the point kept for plain point g, so representative[source_index[k]] == k and a
+ *     visibility word of sdm_extract_points_support (same arguments, index g) can be attached to point k.
+ *     vox->plain_total = T whenever the call gets as far as counting.
+ * `vox` may be NULL, and so may each pointer in it; its pointers follow out->on_device and must be 4-byte aligned there
+ * (multiplicity and source_index hold out->capacity entries, representative rep_capacity).  sdm_point_buffers keeps its
+ * layout; all four field pointers may be NULL if `vox` names a destination.
+ * Errors: those of sdm_extract_points; SDM_EINVAL also for a voxel_size that is not finite and > 0 or whose inv is not
+ * finite (a denormal size), no destination at all, a misaligned device pointer, T >= 2^32 - 1 (in this implementation:
+ * T > 2^30, whose table would pass 2^31 slots), and M > out->capacity or (representative != NULL and
+ * T > rep_capacity) -- in these two cases offsets and plain_total are filled and nothing is written.  SDM_ESTATE on a
+ * context without with_pointset even when out->xyz is NULL: the merge reads the plane.  SDM_EHIP "voxel table overflow"
+ * cannot happen (the probe of a table at most half full always ends) and is reported rather than looped on.
+ * Changes no plane, flag, list or counter, exactly like sdm_extract_points.  Bitwise reproducible from run to run.
+ * Cost: sdm_extract_points' passes with xyz and rho_sigma (plus the requested pixel / intensity) written to an
+ * engine-owned staging, 20 B (+ 4 + 1 B) per plain point; then per plain point one probe of a hash table (three integer
+ * atomics: a 64-bit compare-and-swap, a 64-bit min, a 32-bit add) and 4 B of table position, two more passes over those
+ * 4 B and the 8 B table value, and per KEPT point a gather of the requested fields (12 + 4 + 8 + 1 B read and written)
+ * + 4 B multiplicity + 4 B source_index; 4 B per plain point for representative.  Only the kept points (and the
+ * representative array) cross the link for a host destination, one copy per output of exactly M (T) elements.
+ * Scratch in the context, grown on demand and freed by sdm_destroy: the table has the power of two >= 2 T (at least
+ * 1024) slots of 24 B -- at most 96 B per plain point -- cleared per call on the stream, plus 4 B per plain point.
+ * Three host waits: the plain total T, the kept total M, the end. */
+typedef struct {
+    unsigned *multiplicity;    /* [out->capacity] plain points that fell into the kept point's voxel (1 if unmergeable), or NULL */
+    unsigned *source_index;    /* [out->capacity] index of the kept point in the plain extraction, or NULL */
+    unsigned *representative;  /* [rep_capacity] per PLAIN point: index in the merged cloud of the point kept for it, or NULL */
+    long long rep_capacity;
+    long long plain_total;     /* out: number of points sdm_extract_points returns for the same arguments */
+} sdm_voxel_buffers;
+int sdm_extract_points_voxel(sdm_ctx *ctx, int n, const int *slots, int source, double max_sigma, double min_rho,
+                             float voxel_size, sdm_point_buffers *out, sdm_voxel_buffers *vox /* or NULL */,
+                             long long *offsets);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -41,6 +41,12 @@ class PointBuffers(C.Structure):
                 ("capacity", C.c_longlong), ("on_device", C.c_int)]
 
 
+class VoxelBuffers(C.Structure):
+    """sdm_voxel_buffers"""
+    _fields_ = [("multiplicity", C.c_void_p), ("source_index", C.c_void_p), ("representative", C.c_void_p),
+                ("rep_capacity", C.c_longlong), ("plain_total", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -99,6 +105,8 @@ SYMBOLS = [
                                      C.POINTER(C.c_longlong)]),
     ("sdm_extract_points_support", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double,
                                              C.POINTER(PointBuffers), C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]),
+    ("sdm_extract_points_voxel", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.c_float,
+                                           C.POINTER(PointBuffers), C.POINTER(VoxelBuffers), C.POINTER(C.c_longlong)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -595,6 +603,88 @@ class Engine:
         total = int(offs[n])
         res = {f: a[:total] if known[f][1] == 1 else a.reshape(-1, known[f][1])[:total] for f, a in out.items()}
         res["offsets"] = offs
+        return res
+
+    def extract_points_voxel(self, slots, voxel_size, source=1, max_sigma=0.01, min_rho=1e-6, fields=("xyz",), out=None,
+                             representative=False):
+        """extract_points merged to one point per voxel of edge voxel_size across `slots` (sdm_extract_points_voxel): of the
+        plain points whose cell floor(xyz * (1 / voxel_size)) agrees, the one with the smallest sigma is kept (ties: the
+        earlier slot, then raster order), with its own field values.  Returns {field: array of the m kept points,
+        "offsets": int64[n+1], "multiplicity": uint32[m] plain points in the kept point's voxel, "source_index": uint32[m]
+        its index in extract_points' result, "plain_total": that result's length} plus, with representative=True,
+        "representative": uint32[plain_total], the kept index standing for each plain point.  fields may be empty.
+        out: as for extract_points; it may also carry "multiplicity", "source_index" and "representative" (arrays of
+        4-byte elements; on the device all three must be given if wanted -- none is allocated there).  Too small:
+        SdmError with .offsets and .plain_total.  Without out the buffers are sized by extract_bound."""
+        known = dict(POINT_FIELDS)
+        vox_fields = {"multiplicity": (np.uint32, 1), "source_index": (np.uint32, 1), "representative": (np.uint32, 1)}
+        known.update(vox_fields)
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        n = len(sl)
+        if out is None:
+            for f in fields:
+                if f not in POINT_FIELDS:
+                    raise ValueError("unknown point field %r" % (f,))
+            cap = max(self.extract_bound(sl, source, min_rho), 1)
+            out = {f: np.empty((cap, POINT_FIELDS[f][1]) if POINT_FIELDS[f][1] > 1 else (cap,), POINT_FIELDS[f][0])
+                   for f in fields}
+            for f in ("multiplicity", "source_index") + (("representative",) if representative else ()):
+                out[f] = np.empty(cap, np.uint32)
+        else:
+            out = dict(out)
+            if not any(not isinstance(a, np.ndarray) for a in out.values()):  # host: the vox outputs not given are made here
+                caps = [a.size // known[f][1] for f, a in out.items() if f in known and f != "representative"]
+                need = ("multiplicity", "source_index") + (("representative",) if representative else ())
+                if any(f not in out for f in need):
+                    bound = max(self.extract_bound(sl, source, min_rho), 1)
+                    for f in need:
+                        if f not in out:
+                            out[f] = np.empty(bound if f == "representative" or not caps else min(caps), np.uint32)
+            elif representative and "representative" not in out:
+                raise ValueError('device destinations need a "representative" tensor in out')
+        pb, vb = PointBuffers(), VoxelBuffers()
+        cap, kinds = None, set()
+        for f, a in out.items():
+            if f not in known:
+                raise ValueError("unknown point field %r" % (f,))
+            dt, per = known[f]
+            if isinstance(a, np.ndarray):
+                if a.dtype != dt or not a.flags.c_contiguous or a.size % per:
+                    raise ValueError("%s: need a C-contiguous %s array of [m, %d]" % (f, np.dtype(dt).name, per))
+                kinds.add("host")
+                ptr, m = a.ctypes.data, a.size // per
+            else:  # a torch tensor on this engine's device
+                if not (getattr(a, "is_cuda", False) and a.is_contiguous()) or a.element_size() != np.dtype(dt).itemsize:
+                    raise ValueError("%s: need a contiguous device tensor of %d-byte elements" % (f, np.dtype(dt).itemsize))
+                if a.get_device() != self.device:
+                    raise ValueError("%s: tensor on device %d, engine on device %d" % (f, a.get_device(), self.device))
+                kinds.add("device")
+                ptr, m = a.data_ptr(), a.numel() // per
+            if f == "representative":
+                vb.representative, vb.rep_capacity = ptr, m
+                continue
+            setattr(vb if f in vox_fields else pb, f, ptr)
+            cap = m if cap is None else min(cap, m)
+        if len(kinds) > 1:
+            raise ValueError("out mixes host arrays and device tensors")
+        pb.capacity = cap if cap is not None else 0
+        pb.on_device = 1 if kinds == {"device"} else 0
+        offs = np.zeros(n + 1, np.int64)
+        rc = self.lib.sdm_extract_points_voxel(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma), float(min_rho),
+                                               float(voxel_size), C.byref(pb), C.byref(vb),
+                                               offs.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.offsets = offs
+            e.plain_total = int(vb.plain_total)
+            raise e
+        total, plain = int(offs[n]), int(vb.plain_total)
+        res = {}
+        for f, a in out.items():
+            m = plain if f == "representative" else total
+            res[f] = a[:m] if known[f][1] == 1 else a.reshape(-1, known[f][1])[:m]
+        res["offsets"] = offs
+        res["plain_total"] = plain
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):

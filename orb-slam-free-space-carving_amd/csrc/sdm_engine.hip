@@ -31,6 +31,7 @@
 #include "sdm_support.h"
 #include "sdm_priors.h"
 #include "sdm_covis.h"
+#include "sdm_voxel.h"
 
 using namespace sdm;
 
@@ -239,6 +240,12 @@ struct sdm_ctx {
     size_t ext_host_bytes = 0;
     unsigned char* d_ext_stage = nullptr;
     size_t ext_stage_bytes = 0;
+    // sdm_extract_points_voxel (sdm_voxel.h): hash table, where[], tile counts and offsets; staging of the kept points for
+    // host destinations; each grows on demand
+    unsigned char* d_vox = nullptr;
+    size_t vox_bytes = 0;
+    unsigned char* d_vox_out = nullptr;
+    size_t vox_out_bytes = 0;
 
     // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
     ObsStore obs{};                 // obs.cap != 0 once allocated
@@ -1091,6 +1098,8 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipHostFree(c->h_act_count);
     (void)hipFree(c->d_ext);
     (void)hipFree(c->d_ext_stage);
+    (void)hipFree(c->d_vox);
+    (void)hipFree(c->d_vox_out);
     (void)hipHostFree(c->h_ext);
     (void)hipFree(c->obs.ids);
     (void)hipFree(c->obs.ang);
@@ -2161,11 +2170,25 @@ int sdm_extract_bound(sdm_ctx* c, int n, const int* slots, int source, double mi
     return SDM_OK;
 }
 
+// extract_core's hand-over to sdm_extract_points_voxel: the plain cloud left in the engine's staging, not yet waited for
+struct ExtractStaged {
+    bool pixel, intensity;                 // in: stage these besides xyz and rho_sigma
+    long long total;                       // out: plain points
+    ExtractOut at;                         // out: where they are (d_ext_stage)
+    const unsigned long long* d_offsets;   // out: the plain offsets[n + 1] on the device (d_ext)
+};
+
 // sdm_extract_points (support == nullptr) and sdm_extract_points_support: the three extraction passes, then -- for the
-// second -- k_point_support over the compacted pixel codes (sdm_support.h)
+// second -- k_point_support over the compacted pixel codes (sdm_support.h).  With `st` (sdm_extract_points_voxel; `out`
+// names no destination then): the passes write xyz, rho_sigma and the fields st asks for into the staging whatever the
+// total, and the call returns with pass 3 queued.
 static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
-                        double min_rho, sdm_point_buffers* out, unsigned long long* support, long long* offsets)
+                        double min_rho, sdm_point_buffers* out, unsigned long long* support, long long* offsets,
+                        ExtractStaged* st = nullptr)
 {
+    const bool w_xyz = st || out->xyz, w_pix = st ? st->pixel : out->pixel != nullptr, w_rs = st || out->rho_sigma,
+               w_im = st ? st->intensity : out->intensity != nullptr;
+    if (st) st->total = 0;
     if (out->capacity < 0) return fail(SDM_EINVAL, "negative capacity");
     if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel) % 4 || (uintptr_t)out->rho_sigma % 8))
         return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel: 4 B; rho_sigma: 8 B)");
@@ -2174,7 +2197,7 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     std::vector<int> count;
     int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
     if (rc) return rc;
-    if (out->xyz && !c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
+    if (w_xyz && !c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
     if (support) {  // sdm_inter_check's checks of the neighbour table (the slots themselves: ext_plan)
         if (n_nbr < 1) return fail(SDM_EINVAL, "need at least one neighbour");
         if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
@@ -2251,7 +2274,8 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     HIP_TRY(hipStreamSynchronize(c->stream));  // the one wait in the middle: the total sizes what follows
     for (int i = 0; i <= n; i++) offsets[i] = (long long)h_offs[i];
     const long long total = offsets[n];
-    if (total > out->capacity) return fail(SDM_EINVAL, "capacity " + std::to_string(out->capacity) + " < " +
+    if (st) st->total = total, st->d_offsets = d_offs;
+    if (!st && total > out->capacity) return fail(SDM_EINVAL, "capacity " + std::to_string(out->capacity) + " < " +
                                                            std::to_string(total) + " points (offsets filled)");
     if (total == 0) return SDM_OK;
 
@@ -2259,35 +2283,39 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     // staged for k_point_support when the caller did not ask for them)
     ExtractOut dst;
     unsigned long long* d_sup = nullptr;
-    const bool stage_all = !out->on_device;
+    const bool stage_all = st || !out->on_device;
     const bool stage_pix = support && !out->pixel;
     size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, sup_off = 0;
     {
         const size_t t = (size_t)total;
         size_t at = 0;
-        if (stage_all && out->xyz) xyz_off = at, at += ext_align(12 * t);
-        if ((stage_all && out->pixel) || stage_pix) pix_off = at, at += ext_align(4 * t);
-        if (stage_all && out->rho_sigma) rs_off = at, at += ext_align(8 * t);
-        if (stage_all && out->intensity) im_off = at, at += ext_align(t);
+        if (stage_all && w_xyz) xyz_off = at, at += ext_align(12 * t);
+        if ((stage_all && w_pix) || stage_pix) pix_off = at, at += ext_align(4 * t);
+        if (stage_all && w_rs) rs_off = at, at += ext_align(8 * t);
+        if (stage_all && w_im) im_off = at, at += ext_align(t);
         if (stage_all && support) sup_off = at, at += ext_align(8 * t);
         if (at && (rc = ext_grow_dev(&c->d_ext_stage, &c->ext_stage_bytes, at))) return rc;
     }
     unsigned char* b = c->d_ext_stage;
-    if (out->on_device) {
+    if (!stage_all) {
         dst.xyz = out->xyz;
         dst.pixel = stage_pix ? reinterpret_cast<unsigned*>(b + pix_off) : out->pixel;
         dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
         dst.intensity = out->intensity;
         d_sup = support;
     } else {
-        dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
-        dst.pixel = (out->pixel || stage_pix) ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
-        dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
-        dst.intensity = out->intensity ? b + im_off : nullptr;
+        dst.xyz = w_xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
+        dst.pixel = (w_pix || stage_pix) ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
+        dst.rho_sigma = w_rs ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
+        dst.intensity = w_im ? b + im_off : nullptr;
         d_sup = support ? reinterpret_cast<unsigned long long*>(b + sup_off) : nullptr;
     }
     hipLaunchKernelGGL(k_extract_write, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_toff, d_boff, dst);
     HIP_TRY(hipGetLastError());
+    if (st) {
+        st->at = dst;
+        return SDM_OK;
+    }
     if (support) {
         long long blocks = 0;
         for (int i = 0; i < n; i++) {
@@ -2330,6 +2358,151 @@ int sdm_extract_points_support(sdm_ctx* c, int n, const int* slots, int n_nbr, c
     if (!support) return fail(SDM_EINVAL, "null support");
     if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
     return extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, out, support, offsets);
+}
+
+// ---- one point per voxel (sdm_extract_points_voxel, sdm_voxel.h) -------------------------------------------------------
+int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
+                             float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox, long long* offsets)
+{
+    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
+    if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
+    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(SDM_EINVAL, "voxel_size must be finite and > 0");
+    const float inv = 1.0f / voxel_size;
+    if (!std::isfinite(inv)) return fail(SDM_EINVAL, "1 / voxel_size is not finite");
+    unsigned* mult = vox ? vox->multiplicity : nullptr;
+    unsigned* sidx = vox ? vox->source_index : nullptr;
+    unsigned* repr = vox ? vox->representative : nullptr;
+    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity && !mult && !sidx && !repr)
+        return fail(SDM_EINVAL, "no output requested");
+    if (out->capacity < 0 || (repr && vox->rep_capacity < 0)) return fail(SDM_EINVAL, "negative capacity");
+    if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel | (uintptr_t)mult | (uintptr_t)sidx | (uintptr_t)repr) % 4 ||
+                           (uintptr_t)out->rho_sigma % 8))
+        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel, multiplicity, source_index, representative: 4 B; "
+                                "rho_sigma: 8 B)");
+
+    // the plain cloud into the staging (xyz and rho_sigma feed the merge whatever the caller asks for)
+    ExtractStaged st{};
+    st.pixel = out->pixel != nullptr;
+    st.intensity = out->intensity != nullptr;
+    sdm_point_buffers none{};
+    std::vector<long long> plain((size_t)n + 1, 0);
+    int rc = extract_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
+    if (rc) return rc;
+    const long long T = st.total;
+    if (vox) vox->plain_total = T;
+    if (T >= 0xffffffffll) return fail(SDM_EINVAL, "2^32 - 1 or more plain points in one call");
+    if (T == 0) {  // (extract_core has waited for the stream)
+        for (int i = 0; i <= n; i++) offsets[i] = 0;
+        return SDM_OK;
+    }
+    unsigned long long cap = 1024;
+    while (cap < 2ull * (unsigned long long)T) cap <<= 1;
+    if (cap > (1ull << 31)) return fail(SDM_EINVAL, "more than 2^30 plain points: the voxel table would exceed 2^31 slots");
+
+    const long long vt = (T + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t key_b = 8 * (size_t)cap, cnt_b = 4 * (size_t)cap + 256 /* + the overflow flag */, rank_b = 4 * (size_t)cap;
+    const size_t where_b = ext_align(4 * (size_t)T), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
+    const size_t blk_b = ext_align(8 * (size_t)vb), offs_b = ext_align(8 * (size_t)(n + 2));
+    if ((rc = ext_grow_dev(&c->d_vox, &c->vox_bytes, 2 * key_b + cnt_b + rank_b + where_b + tcnt_b + toff_b + 2 * blk_b + offs_b)))
+        return rc;
+    if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, offs_b))) return rc;  // (the plain passes are done with it)
+    unsigned char* p = c->d_vox;
+    VoxTable tb;
+    tb.keys = reinterpret_cast<unsigned long long*>(p), p += key_b;
+    tb.vals = reinterpret_cast<unsigned long long*>(p), p += key_b;
+    tb.cnt = reinterpret_cast<unsigned*>(p);
+    unsigned* d_flag = reinterpret_cast<unsigned*>(p + 4 * (size_t)cap);
+    p += cnt_b;
+    tb.rank = reinterpret_cast<unsigned*>(p), p += rank_b;
+    tb.mask = cap - 1;
+    unsigned* d_where = reinterpret_cast<unsigned*>(p);
+    p += where_b;
+    unsigned* d_tcnt = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_toff = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_voffs = reinterpret_cast<unsigned long long*>(p);
+    unsigned long long* h_voffs = reinterpret_cast<unsigned long long*>(c->h_ext);
+
+    HIP_TRY(hipMemsetAsync(tb.keys, 0xff, 2 * key_b, c->stream));  // keys: VOX_EMPTY; values: the minimum's identity
+    HIP_TRY(hipMemsetAsync(tb.cnt, 0, cnt_b, c->stream));           // counts and the flag
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long pblocks = (T + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_voxel_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, st.at.xyz,
+                           st.at.rho_sigma, T, b0 * BLOCK, inv, tb, d_where, d_flag);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_voxel_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0,
+                           d_tcnt);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_tcnt, vt, d_toff, d_bsum);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)vb, d_boff);
+    hipLaunchKernelGGL(k_voxel_offsets, dim3((unsigned)(n + 2)), dim3(BLOCK), 0, c->stream, tb, d_where, T, st.d_offsets, n, vt,
+                       d_toff, d_boff, d_flag, d_voffs);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_voffs, d_voffs, 8 * (size_t)(n + 2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the kept total sizes what follows
+    if (h_voffs[n + 1]) return fail(SDM_EHIP, "voxel table overflow");
+    for (int i = 0; i <= n; i++) offsets[i] = (long long)h_voffs[i];
+    const long long M = offsets[n];
+    if (M > out->capacity) return fail(SDM_EINVAL, "capacity " + std::to_string(out->capacity) + " < " + std::to_string(M) +
+                                                       " points (offsets and plain_total filled)");
+    if (repr && T > vox->rep_capacity)
+        return fail(SDM_EINVAL, "rep_capacity " + std::to_string(vox->rep_capacity) + " < " + std::to_string(T) +
+                                    " plain points (offsets and plain_total filled)");
+
+    // where the kept points go: the caller's device buffers, or one staging region per requested output
+    ExtractOut dst;
+    unsigned *d_mult = mult, *d_sidx = sidx, *d_repr = repr;
+    if (out->on_device) {
+        dst.xyz = out->xyz;
+        dst.pixel = out->pixel;
+        dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
+        dst.intensity = out->intensity;
+    } else {
+        const size_t m = (size_t)M;
+        size_t at = 0, xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, mult_off = 0, sidx_off = 0, repr_off = 0;
+        if (out->xyz) xyz_off = at, at += ext_align(12 * m);
+        if (out->pixel) pix_off = at, at += ext_align(4 * m);
+        if (out->rho_sigma) rs_off = at, at += ext_align(8 * m);
+        if (out->intensity) im_off = at, at += ext_align(m);
+        if (mult) mult_off = at, at += ext_align(4 * m);
+        if (sidx) sidx_off = at, at += ext_align(4 * m);
+        if (repr) repr_off = at, at += ext_align(4 * (size_t)T);
+        if ((rc = ext_grow_dev(&c->d_vox_out, &c->vox_out_bytes, at))) return rc;
+        unsigned char* b = c->d_vox_out;
+        dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
+        dst.pixel = out->pixel ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
+        dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
+        dst.intensity = out->intensity ? b + im_off : nullptr;
+        d_mult = mult ? reinterpret_cast<unsigned*>(b + mult_off) : nullptr;
+        d_sidx = sidx ? reinterpret_cast<unsigned*>(b + sidx_off) : nullptr;
+        d_repr = repr ? reinterpret_cast<unsigned*>(b + repr_off) : nullptr;
+    }
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_voxel_write, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0,
+                           d_toff, d_boff, st.at, dst, d_mult, d_sidx, d_repr);
+    if (repr)
+        for (long long b0 = 0; b0 < pblocks; b0 += per)
+            hipLaunchKernelGGL(k_voxel_rep, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, tb, d_where,
+                               T, b0 * BLOCK, d_repr);
+    HIP_TRY(hipGetLastError());
+    if (!out->on_device) {
+        const size_t m = (size_t)M;
+        if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, dst.xyz, 12 * m, hipMemcpyDeviceToHost, c->stream));
+        if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, dst.pixel, 4 * m, hipMemcpyDeviceToHost, c->stream));
+        if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, dst.rho_sigma, 8 * m, hipMemcpyDeviceToHost, c->stream));
+        if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, dst.intensity, m, hipMemcpyDeviceToHost, c->stream));
+        if (mult) HIP_TRY(hipMemcpyAsync(mult, d_mult, 4 * m, hipMemcpyDeviceToHost, c->stream));
+        if (sidx) HIP_TRY(hipMemcpyAsync(sidx, d_sidx, 4 * m, hipMemcpyDeviceToHost, c->stream));
+        if (repr) HIP_TRY(hipMemcpyAsync(repr, d_repr, 4 * (size_t)T, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the third wait
+    return SDM_OK;
 }
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
