@@ -363,6 +363,55 @@ typedef struct {
 int sdm_extract_points_voxel(sdm_ctx *ctx, int n, const int *slots, int source, double max_sigma, double min_rho,
                              float voxel_size, sdm_point_buffers *out, sdm_voxel_buffers *vox /* or NULL */,
                              long long *offsets);
+/* sdm_extract_points_voxel plus, per KEPT point, the cameras that saw the surface element it stands for: the
+ * `new point: [x; y; z], KF_ind1, ..., KF_indN` of the transcript for the merged cloud.  Bit j of a support word names a
+ * different keyframe for every slot, so the words of a voxel's points cannot be OR-ed; this call resolves them to slot
+ * ids on the device and returns one list per kept point (tests/voxcam_np.py restates it in NumPy).
+ *   - Unchanged outputs: the points, their order, offsets, the fields of `out` and the outputs of `vox` are exactly those
+ *     of sdm_extract_points_voxel for the same (slots, source, max_sigma, min_rho, voxel_size).
+ *   - Support words: with support[g] the word sdm_extract_points_support returns for the same (slots, n_nbr, nbr_slots,
+ *     source, max_sigma, min_rho) at plain index g, and i(g) the position in `slots` of the slot of g,
+ *         C(g) = { slots[i(g)] } U { nbr_slots[i(g)][j] : bit j of support[g] }.
+ *     The observing keyframe is always a member, also when the word is 0 (outside the inset, skipped by PM.cc:662) and
+ *     for an unmergeable point.
+ *   - Merged list: V(k) = U { C(g) : representative[g] == k }.  The list of kept point k is V(k) as slot ids in strictly
+ *     ascending order, without duplicates: cam_slots[cam_offsets[k] .. cam_offsets[k + 1]).  A repeated neighbour and a
+ *     neighbour equal to the point's own slot fall out of the union; any neighbour table sdm_extract_points_support
+ *     accepts is accepted here.
+ *   - Offsets: cam_offsets[0] = 0 and cam_offsets[M] = cam_total = E, the sum of the list lengths.
+ *   - Arithmetic: integer only; a pure function of the arguments and the planes, bitwise reproducible from run to run.
+ *     Changes no plane, flag, list or counter, except sdm_stats::table_stagings as sdm_extract_points_support does (the
+ *     staged set is shared with an sdm_inter_check over the same lists).
+ * `cams` must not be NULL and at least one of its two pointers must not be.  With cam_slots == NULL the call returns the
+ * offsets (the list lengths) only and cam_capacity is ignored.  The pointers follow out->on_device: cam_offsets 8-byte,
+ * cam_slots 4-byte aligned there; cam_offsets holds out->capacity + 1 entries.  `out` and `vox` may name no destination
+ * at all.
+ * Errors: the union of sdm_extract_points_voxel's and sdm_extract_points_support's (NULL cams / nbr_slots, no camera
+ * pointer, a negative cam_capacity, a misaligned device pointer, n_nbr < 1 or > max_neighbours, a neighbour slot out of
+ * range: SDM_EINVAL; a neighbour without a depth map: SDM_ESTATE), all checked on the host before anything is queued.
+ *   - M > out->capacity and (representative != NULL and T > rep_capacity) come first and keep their contract: offsets
+ *     and plain_total filled, nothing written, cam_total = 0.
+ *   - E > cam_capacity with cam_slots != NULL: SDM_EINVAL with offsets, plain_total and cam_total filled; neither camera
+ *     array is written, the content of the other destinations is unspecified.  Size cam_slots and call again.
+ *   - SDM_EINVAL also when min(M, 2^22) x (distinct slots of the call) >= 2^32: the list pass scans 32-bit sums.
+ * Cost on top of sdm_extract_points_voxel: sdm_extract_points_support's pass over the T plain points (4 B of staged pixel
+ * codes and 8 B of support word per plain point) and, when the caller takes no `representative`, its 4 B per plain
+ * point in engine scratch; then per plain point 12 B read (word, rank) and at most Wd = ceil(Cn / 64) 64-bit atomic ORs,
+ * Cn the distinct slots among slots and nbr_slots -- the lanes of a wave that share a kept point combine first, so a
+ * run of equal ranks issues one atomic per word; per kept point Wd x 8 B of bitset (cleared per call on the stream, read
+ * twice), 8 B of offset and 4 B per list entry written.  Only cam_offsets (8 (M + 1) B) and cam_slots (4 E B) cross the
+ * link for a host destination.  Scratch lives in the context, grows on demand and is freed by sdm_destroy.
+ * Four host waits: the plain total T, the kept total M, the lists' total E, the end. */
+typedef struct {
+    long long *cam_offsets;   /* [out->capacity + 1]: list of kept point k = cam_slots[cam_offsets[k] .. cam_offsets[k+1]), or NULL */
+    int *cam_slots;           /* [cam_capacity] slot ids, or NULL */
+    long long cam_capacity;
+    long long cam_total;      /* out: sum of the list lengths E */
+} sdm_voxel_cameras;
+int sdm_extract_points_voxel_cameras(sdm_ctx *ctx, int n, const int *slots, int n_nbr, const int *nbr_slots /*[n][n_nbr]*/,
+                                     int source, double max_sigma, double min_rho, float voxel_size,
+                                     sdm_point_buffers *out, sdm_voxel_buffers *vox /* or NULL */,
+                                     sdm_voxel_cameras *cams, long long *offsets);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -47,6 +47,12 @@ class VoxelBuffers(C.Structure):
                 ("rep_capacity", C.c_longlong), ("plain_total", C.c_longlong)]
 
 
+class VoxelCameras(C.Structure):
+    """sdm_voxel_cameras"""
+    _fields_ = [("cam_offsets", C.c_void_p), ("cam_slots", C.c_void_p), ("cam_capacity", C.c_longlong),
+                ("cam_total", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -107,6 +113,9 @@ SYMBOLS = [
                                              C.POINTER(PointBuffers), C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]),
     ("sdm_extract_points_voxel", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.c_float,
                                            C.POINTER(PointBuffers), C.POINTER(VoxelBuffers), C.POINTER(C.c_longlong)]),
+    ("sdm_extract_points_voxel_cameras", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.c_float,
+                                                   C.POINTER(PointBuffers), C.POINTER(VoxelBuffers),
+                                                   C.POINTER(VoxelCameras), C.POINTER(C.c_longlong)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -616,16 +625,48 @@ class Engine:
         out: as for extract_points; it may also carry "multiplicity", "source_index" and "representative" (arrays of
         4-byte elements; on the device all three must be given if wanted -- none is allocated there).  Too small:
         SdmError with .offsets and .plain_total.  Without out the buffers are sized by extract_bound."""
+        return self._extract_voxel(slots, None, voxel_size, source, max_sigma, min_rho, fields, out, representative)
+
+    def extract_points_voxel_cameras(self, slots, nbrs, voxel_size, source=1, max_sigma=0.01, min_rho=1e-6, fields=("xyz",),
+                                     out=None, representative=False):
+        """extract_points_voxel plus, per kept point, the cameras that saw the points it stands for
+        (sdm_extract_points_voxel_cameras): the union over the kept point's voxel of {the point's own slot} and the
+        neighbours nbrs[i][j] whose bit j is set in the point's extract_points_support word, as slot ids in ascending
+        order.  Returns extract_points_voxel's dictionary plus "cam_offsets": int64[m + 1], "cam_slots": int32[cam_total]
+        (the list of kept point k is cam_slots[cam_offsets[k]:cam_offsets[k + 1]]) and "cam_total".  out: as for
+        extract_points_voxel; it may also carry "cam_offsets" (8-byte elements, one more than the points) and "cam_slots"
+        (4-byte elements) -- host arrays not given are made here; on the device at least one of the two must be given and
+        only those given are filled.  A cam_slots made here holds min(bound * (1 + n_nbr), 2**26) entries, and the call is
+        repeated once with the reported total if that was too few.  Too small: SdmError with .offsets, .plain_total and
+        .cam_total."""
+        sl = np.asarray(slots, dtype=np.int32).reshape(-1)
+        nb = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(len(sl), -1)
+        return self._extract_voxel(sl, nb, voxel_size, source, max_sigma, min_rho, fields, out, representative)
+
+    def _extract_voxel(self, slots, nbrs, voxel_size, source, max_sigma, min_rho, fields, out, representative, cam_entries=None):
         known = dict(POINT_FIELDS)
         vox_fields = {"multiplicity": (np.uint32, 1), "source_index": (np.uint32, 1), "representative": (np.uint32, 1)}
+        cam_fields = {"cam_offsets": (np.int64, 1), "cam_slots": (np.int32, 1)} if nbrs is not None else {}
         known.update(vox_fields)
+        known.update(cam_fields)
         sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
         n = len(sl)
+        given, made_slots = out, False
+
+        def size_bound():  # (a refusal while sizing carries what a refusal of the call itself carries)
+            try:
+                return max(self.extract_bound(sl, source, min_rho), 1)
+            except SdmError as e:
+                e.offsets, e.plain_total = np.zeros(n + 1, np.int64), 0
+                if nbrs is not None:
+                    e.cam_total = 0
+                raise
+
         if out is None:
             for f in fields:
                 if f not in POINT_FIELDS:
                     raise ValueError("unknown point field %r" % (f,))
-            cap = max(self.extract_bound(sl, source, min_rho), 1)
+            cap = size_bound()
             out = {f: np.empty((cap, POINT_FIELDS[f][1]) if POINT_FIELDS[f][1] > 1 else (cap,), POINT_FIELDS[f][0])
                    for f in fields}
             for f in ("multiplicity", "source_index") + (("representative",) if representative else ()):
@@ -633,16 +674,29 @@ class Engine:
         else:
             out = dict(out)
             if not any(not isinstance(a, np.ndarray) for a in out.values()):  # host: the vox outputs not given are made here
-                caps = [a.size // known[f][1] for f, a in out.items() if f in known and f != "representative"]
+                caps = [a.size - 1 if f == "cam_offsets" else a.size // known[f][1] for f, a in out.items()
+                        if f in known and f not in ("representative", "cam_slots")]
                 need = ("multiplicity", "source_index") + (("representative",) if representative else ())
                 if any(f not in out for f in need):
-                    bound = max(self.extract_bound(sl, source, min_rho), 1)
+                    bound = size_bound()
                     for f in need:
                         if f not in out:
                             out[f] = np.empty(bound if f == "representative" or not caps else min(caps), np.uint32)
             elif representative and "representative" not in out:
                 raise ValueError('device destinations need a "representative" tensor in out')
-        pb, vb = PointBuffers(), VoxelBuffers()
+            elif cam_fields and not any(f in out for f in cam_fields):
+                raise ValueError('device destinations need a "cam_offsets" or a "cam_slots" tensor in out')
+        if cam_fields and not any(not isinstance(a, np.ndarray) for a in out.values()):  # host: the lists not given are made here
+            if "cam_offsets" not in out or "cam_slots" not in out:
+                caps = [a.size // known[f][1] for f, a in out.items() if f not in ("representative", "cam_slots", "cam_offsets")]
+                bound = size_bound()
+                if "cam_offsets" not in out:
+                    out["cam_offsets"] = np.empty((min(caps) if caps else bound) + 1, np.int64)
+                if "cam_slots" not in out:
+                    made_slots = True
+                    entries = cam_entries if cam_entries is not None else min(bound * (1 + nbrs.shape[1]), 1 << 26)
+                    out["cam_slots"] = np.empty(max(entries, 1), np.int32)
+        pb, vb, vc = PointBuffers(), VoxelBuffers(), VoxelCameras()
         cap, kinds = None, set()
         for f, a in out.items():
             if f not in known:
@@ -663,28 +717,50 @@ class Engine:
             if f == "representative":
                 vb.representative, vb.rep_capacity = ptr, m
                 continue
-            setattr(vb if f in vox_fields else pb, f, ptr)
+            if f == "cam_slots":
+                vc.cam_slots, vc.cam_capacity = ptr, m
+                continue
+            if f == "cam_offsets":
+                if m < 1:
+                    raise ValueError("cam_offsets: need at least one entry")
+                vc.cam_offsets, m = ptr, m - 1  # (one entry more than the points)
+            else:
+                setattr(vb if f in vox_fields else pb, f, ptr)
             cap = m if cap is None else min(cap, m)
         if len(kinds) > 1:
             raise ValueError("out mixes host arrays and device tensors")
         pb.capacity = cap if cap is not None else 0
         pb.on_device = 1 if kinds == {"device"} else 0
         offs = np.zeros(n + 1, np.int64)
-        rc = self.lib.sdm_extract_points_voxel(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma), float(min_rho),
-                                               float(voxel_size), C.byref(pb), C.byref(vb),
-                                               offs.ctypes.data_as(C.POINTER(C.c_longlong)))
+        offp = offs.ctypes.data_as(C.POINTER(C.c_longlong))
+        if nbrs is None:
+            rc = self.lib.sdm_extract_points_voxel(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma),
+                                                   float(min_rho), float(voxel_size), C.byref(pb), C.byref(vb), offp)
+        else:
+            rc = self.lib.sdm_extract_points_voxel_cameras(self.ctx, n, sl.ctypes.data_as(_ip), nbrs.shape[1],
+                                                           nbrs.ctypes.data_as(_ip), int(source), float(max_sigma),
+                                                           float(min_rho), float(voxel_size), C.byref(pb), C.byref(vb),
+                                                           C.byref(vc), offp)
         if rc:
+            if made_slots and cam_entries is None and int(vc.cam_total) > int(vc.cam_capacity):
+                # the cam_slots made here was too small: once more with the reported total
+                return self._extract_voxel(slots, nbrs, voxel_size, source, max_sigma, min_rho, fields, given, representative,
+                                           cam_entries=int(vc.cam_total))
             e = SdmError(rc, self.lib.sdm_last_error().decode())
             e.offsets = offs
             e.plain_total = int(vb.plain_total)
+            if nbrs is not None:
+                e.cam_total = int(vc.cam_total)
             raise e
         total, plain = int(offs[n]), int(vb.plain_total)
         res = {}
         for f, a in out.items():
-            m = plain if f == "representative" else total
+            m = {"representative": plain, "cam_offsets": total + 1, "cam_slots": int(vc.cam_total)}.get(f, total)
             res[f] = a[:m] if known[f][1] == 1 else a.reshape(-1, known[f][1])[:m]
         res["offsets"] = offs
         res["plain_total"] = plain
+        if nbrs is not None:
+            res["cam_total"] = int(vc.cam_total)
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):

@@ -32,6 +32,7 @@
 #include "sdm_priors.h"
 #include "sdm_covis.h"
 #include "sdm_voxel.h"
+#include "sdm_voxcam.h"
 
 using namespace sdm;
 
@@ -246,6 +247,14 @@ struct sdm_ctx {
     size_t vox_bytes = 0;
     unsigned char* d_vox_out = nullptr;
     size_t vox_out_bytes = 0;
+    // sdm_extract_points_voxel_cameras (sdm_voxcam.h): camera table, ranks, bitsets, tile counts and offsets; staging of
+    // the lists for host destinations; pinned mirror of the camera table and the total; each grows on demand
+    unsigned char* d_vcam = nullptr;
+    size_t vcam_bytes = 0;
+    unsigned char* d_vcam_out = nullptr;
+    size_t vcam_out_bytes = 0;
+    unsigned char* h_vcam = nullptr;
+    size_t vcam_host_bytes = 0;
 
     // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
     ObsStore obs{};                 // obs.cap != 0 once allocated
@@ -1100,6 +1109,9 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->d_ext_stage);
     (void)hipFree(c->d_vox);
     (void)hipFree(c->d_vox_out);
+    (void)hipFree(c->d_vcam);
+    (void)hipFree(c->d_vcam_out);
+    (void)hipHostFree(c->h_vcam);
     (void)hipHostFree(c->h_ext);
     (void)hipFree(c->obs.ids);
     (void)hipFree(c->obs.ang);
@@ -2173,21 +2185,26 @@ int sdm_extract_bound(sdm_ctx* c, int n, const int* slots, int source, double mi
 // extract_core's hand-over to sdm_extract_points_voxel: the plain cloud left in the engine's staging, not yet waited for
 struct ExtractStaged {
     bool pixel, intensity;                 // in: stage these besides xyz and rho_sigma
+    bool support;                          // in: stage the pixel codes and the support words too (k_point_support queued)
     long long total;                       // out: plain points
     ExtractOut at;                         // out: where they are (d_ext_stage)
     const unsigned long long* d_offsets;   // out: the plain offsets[n + 1] on the device (d_ext)
+    const unsigned long long* d_support;   // out (support): the words (d_ext_stage)
+    const long long* d_block0;             // out (support): k_point_support's block0[n + 1] on the device (d_ext)
+    long long blocks;                      // out (support): its workgroups
 };
 
 // sdm_extract_points (support == nullptr) and sdm_extract_points_support: the three extraction passes, then -- for the
 // second -- k_point_support over the compacted pixel codes (sdm_support.h).  With `st` (sdm_extract_points_voxel; `out`
 // names no destination then): the passes write xyz, rho_sigma and the fields st asks for into the staging whatever the
-// total, and the call returns with pass 3 queued.
+// total, and the call returns with pass 3 (and, if st asks for the words, k_point_support) queued.
 static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
                         double min_rho, sdm_point_buffers* out, unsigned long long* support, long long* offsets,
                         ExtractStaged* st = nullptr)
 {
     const bool w_xyz = st || out->xyz, w_pix = st ? st->pixel : out->pixel != nullptr, w_rs = st || out->rho_sigma,
                w_im = st ? st->intensity : out->intensity != nullptr;
+    const bool w_sup = support || (st && st->support);
     if (st) st->total = 0;
     if (out->capacity < 0) return fail(SDM_EINVAL, "negative capacity");
     if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel) % 4 || (uintptr_t)out->rho_sigma % 8))
@@ -2198,7 +2215,7 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
     if (rc) return rc;
     if (w_xyz && !c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
-    if (support) {  // sdm_inter_check's checks of the neighbour table (the slots themselves: ext_plan)
+    if (w_sup) {  // sdm_inter_check's checks of the neighbour table (the slots themselves: ext_plan)
         if (n_nbr < 1) return fail(SDM_EINVAL, "need at least one neighbour");
         if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
         for (size_t i = 0; i < (size_t)n * (size_t)n_nbr; i++) {
@@ -2212,11 +2229,11 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     HIP_TRY(hipSetDevice(c->cfg.device));
     // RefConst / PairConst of the call (the set an sdm_inter_check over the same lists staged serves this call too); the
     // lists are left as they are: this call changes none
-    if (support && n > 0 && (rc = stage_tables(c, n, slots, n_nbr, nbr_slots, nullptr, nullptr, nullptr, false, false))) return rc;
+    if (w_sup && n > 0 && (rc = stage_tables(c, n, slots, n_nbr, nbr_slots, nullptr, nullptr, nullptr, false, false))) return rc;
 
     const size_t tab_b = ext_align(sizeof(ExtractSlot) * (size_t)std::max(n, 1));
     const size_t offs_b = ext_align(sizeof(unsigned long long) * (size_t)(n + 1));
-    const size_t cut_b = support ? ext_align(sizeof(long long) * (size_t)(n + 1)) : 0;  // first workgroup per slot (k_point_support's block0)
+    const size_t cut_b = w_sup ? ext_align(sizeof(long long) * (size_t)(n + 1)) : 0;  // first workgroup per slot (k_point_support's block0)
     if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, tab_b + offs_b + cut_b))) return rc;
     ExtractSlot* h_tab = reinterpret_cast<ExtractSlot*>(c->h_ext);
     unsigned long long* h_offs = reinterpret_cast<unsigned long long*>(c->h_ext + tab_b);
@@ -2284,7 +2301,7 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     ExtractOut dst;
     unsigned long long* d_sup = nullptr;
     const bool stage_all = st || !out->on_device;
-    const bool stage_pix = support && !out->pixel;
+    const bool stage_pix = w_sup && !out->pixel;
     size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, sup_off = 0;
     {
         const size_t t = (size_t)total;
@@ -2293,7 +2310,7 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
         if ((stage_all && w_pix) || stage_pix) pix_off = at, at += ext_align(4 * t);
         if (stage_all && w_rs) rs_off = at, at += ext_align(8 * t);
         if (stage_all && w_im) im_off = at, at += ext_align(t);
-        if (stage_all && support) sup_off = at, at += ext_align(8 * t);
+        if (stage_all && w_sup) sup_off = at, at += ext_align(8 * t);
         if (at && (rc = ext_grow_dev(&c->d_ext_stage, &c->ext_stage_bytes, at))) return rc;
     }
     unsigned char* b = c->d_ext_stage;
@@ -2308,15 +2325,11 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
         dst.pixel = (w_pix || stage_pix) ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
         dst.rho_sigma = w_rs ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
         dst.intensity = w_im ? b + im_off : nullptr;
-        d_sup = support ? reinterpret_cast<unsigned long long*>(b + sup_off) : nullptr;
+        d_sup = w_sup ? reinterpret_cast<unsigned long long*>(b + sup_off) : nullptr;
     }
     hipLaunchKernelGGL(k_extract_write, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_toff, d_boff, dst);
     HIP_TRY(hipGetLastError());
-    if (st) {
-        st->at = dst;
-        return SDM_OK;
-    }
-    if (support) {
+    if (w_sup) {
         long long blocks = 0;
         for (int i = 0; i < n; i++) {
             h_cut[i] = blocks;
@@ -2329,6 +2342,11 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
             hipLaunchKernelGGL(k_point_support, dim3((unsigned)std::min(per, blocks - b0)), dim3(SUP_BLOCK), 0, c->stream,
                                c->pool, c->P, c->d_refs, c->d_pairs, n, n_nbr, c->W, c->H, d_cut, b0, d_offs, dst.pixel, d_sup);
         HIP_TRY(hipGetLastError());
+        if (st) st->d_support = d_sup, st->d_block0 = d_cut, st->blocks = blocks;
+    }
+    if (st) {
+        st->at = dst;
+        return SDM_OK;
     }
     if (!out->on_device) {
         const size_t t = (size_t)total;
@@ -2360,19 +2378,28 @@ int sdm_extract_points_support(sdm_ctx* c, int n, const int* slots, int n_nbr, c
     return extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, out, support, offsets);
 }
 
-// ---- one point per voxel (sdm_extract_points_voxel, sdm_voxel.h) -------------------------------------------------------
-int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
-                             float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox, long long* offsets)
+// ---- one point per voxel (sdm_extract_points_voxel, sdm_voxel.h; with `cams` sdm_extract_points_voxel_cameras,
+// sdm_voxcam.h: the neighbour table is read only then) -----------------------------------------------------------------
+static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
+                      double min_rho, float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox,
+                      sdm_voxel_cameras* cams, long long* offsets)
 {
     if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
     if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
+    if (cams) {
+        if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
+        if (!cams->cam_offsets && !cams->cam_slots) return fail(SDM_EINVAL, "no camera output requested");
+        if (cams->cam_slots && cams->cam_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
+        if (out->on_device && ((uintptr_t)cams->cam_offsets % 8 || (uintptr_t)cams->cam_slots % 4))
+            return fail(SDM_EINVAL, "device buffer not aligned (cam_offsets: 8 B; cam_slots: 4 B)");
+    }
     if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(SDM_EINVAL, "voxel_size must be finite and > 0");
     const float inv = 1.0f / voxel_size;
     if (!std::isfinite(inv)) return fail(SDM_EINVAL, "1 / voxel_size is not finite");
     unsigned* mult = vox ? vox->multiplicity : nullptr;
     unsigned* sidx = vox ? vox->source_index : nullptr;
     unsigned* repr = vox ? vox->representative : nullptr;
-    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity && !mult && !sidx && !repr)
+    if (!cams && !out->xyz && !out->pixel && !out->rho_sigma && !out->intensity && !mult && !sidx && !repr)
         return fail(SDM_EINVAL, "no output requested");
     if (out->capacity < 0 || (repr && vox->rep_capacity < 0)) return fail(SDM_EINVAL, "negative capacity");
     if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel | (uintptr_t)mult | (uintptr_t)sidx | (uintptr_t)repr) % 4 ||
@@ -2384,15 +2411,25 @@ int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, do
     ExtractStaged st{};
     st.pixel = out->pixel != nullptr;
     st.intensity = out->intensity != nullptr;
+    st.support = cams != nullptr;
     sdm_point_buffers none{};
     std::vector<long long> plain((size_t)n + 1, 0);
-    int rc = extract_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
+    int rc = extract_core(c, n, slots, cams ? n_nbr : 0, cams ? nbr_slots : nullptr, source, max_sigma, min_rho, &none,
+                          nullptr, plain.data(), &st);
     if (rc) return rc;
     const long long T = st.total;
     if (vox) vox->plain_total = T;
     if (T >= 0xffffffffll) return fail(SDM_EINVAL, "2^32 - 1 or more plain points in one call");
     if (T == 0) {  // (extract_core has waited for the stream)
         for (int i = 0; i <= n; i++) offsets[i] = 0;
+        if (cams && cams->cam_offsets) {  // no kept point: the one entry cam_offsets[0] = 0
+            if (out->on_device) {
+                HIP_TRY(hipMemsetAsync(cams->cam_offsets, 0, sizeof(long long), c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+            } else {
+                cams->cam_offsets[0] = 0;
+            }
+        }
         return SDM_OK;
     }
     unsigned long long cap = 1024;
@@ -2445,6 +2482,26 @@ int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, do
                        d_toff, d_boff, d_flag, d_voffs);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_voffs, d_voffs, 8 * (size_t)(n + 2), hipMemcpyDeviceToHost, c->stream));
+    // the camera table (sdm_voxcam.h), built while the passes run: the distinct slots of the call in ascending order, and
+    // per row the camera index of its own slot and of its neighbours (extract_core has checked every slot's range);
+    // h_vcam = the total E read back | slot_of_cam[Cn] own_cam[n] nbr_cam[n][n_nbr]
+    int Cn = 0;
+    size_t cam_tab_n = 0;
+    if (cams) {
+        const size_t np = (size_t)n * (size_t)n_nbr;
+        std::vector<int> cam_of((size_t)c->cfg.max_keyframes, -1);
+        for (int i = 0; i < n; i++) cam_of[(size_t)slots[i]] = 0;
+        for (size_t i = 0; i < np; i++) cam_of[(size_t)nbr_slots[i]] = 0;
+        for (int s = 0; s < c->cfg.max_keyframes; s++)
+            if (cam_of[(size_t)s] == 0) cam_of[(size_t)s] = Cn++;
+        cam_tab_n = (size_t)Cn + (size_t)n + np;
+        if ((rc = ext_grow_host(&c->h_vcam, &c->vcam_host_bytes, 256 + 4 * cam_tab_n))) return rc;
+        int* h_tab = reinterpret_cast<int*>(c->h_vcam + 256);
+        for (int s = 0; s < c->cfg.max_keyframes; s++)
+            if (cam_of[(size_t)s] >= 0) h_tab[cam_of[(size_t)s]] = s;
+        for (int i = 0; i < n; i++) h_tab[Cn + i] = cam_of[(size_t)slots[i]];
+        for (size_t i = 0; i < np; i++) h_tab[(size_t)Cn + (size_t)n + i] = cam_of[(size_t)nbr_slots[i]];
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the kept total sizes what follows
     if (h_voffs[n + 1]) return fail(SDM_EHIP, "voxel table overflow");
     for (int i = 0; i <= n; i++) offsets[i] = (long long)h_voffs[i];
@@ -2483,14 +2540,97 @@ int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, do
         d_sidx = sidx ? reinterpret_cast<unsigned*>(b + sidx_off) : nullptr;
         d_repr = repr ? reinterpret_cast<unsigned*>(b + repr_off) : nullptr;
     }
+    // (cams) scratch: the staged camera table, every plain point's kept rank when the caller takes no `representative`,
+    // the bitsets, the tile counts and their scan; grown before anything that reads it is queued
+    unsigned* d_rank = d_repr;
+    const int Wd = (Cn + 63) / 64;
+    const long long kt = (M + EXT_TILE - 1) / EXT_TILE;
+    const long long kb = (kt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    VoxCamTable ctab{};
+    unsigned long long *d_bits = nullptr, *d_kbsum = nullptr, *d_kboff = nullptr, *d_E = nullptr;
+    unsigned *d_ktcnt = nullptr, *d_ktoff = nullptr;
+    if (cams) {
+        // the scan keeps 32-bit sums per EXT_SCAN tiles (k_extract_scan_tiles): a kept point has at most Cn cameras
+        if ((unsigned long long)std::min(M, (long long)EXT_TILE * EXT_SCAN) * (unsigned long long)Cn >= (1ull << 32))
+            return fail(SDM_EINVAL, "camera lists of 2^22 kept points could pass 2^32 entries: too many distinct slots in one call");
+        const size_t tab_b = ext_align(4 * cam_tab_n), rank_b = d_repr ? 0 : ext_align(4 * (size_t)T);
+        const size_t bits_b = ext_align(8 * (size_t)M * (size_t)Wd), ktcnt_b = ext_align(4 * (size_t)kt);
+        const size_t ktoff_b = ext_align(4 * (size_t)(kt + 1)), kblk_b = ext_align(8 * (size_t)kb);
+        if ((rc = ext_grow_dev(&c->d_vcam, &c->vcam_bytes, tab_b + rank_b + bits_b + ktcnt_b + ktoff_b + 2 * kblk_b + 256)))
+            return rc;
+        unsigned char* q = c->d_vcam;
+        int* d_ctab = reinterpret_cast<int*>(q);
+        q += tab_b;
+        if (!d_repr) d_rank = reinterpret_cast<unsigned*>(q);
+        q += rank_b;
+        d_bits = reinterpret_cast<unsigned long long*>(q), q += bits_b;
+        d_ktcnt = reinterpret_cast<unsigned*>(q), q += ktcnt_b;
+        d_ktoff = reinterpret_cast<unsigned*>(q), q += ktoff_b;
+        d_kbsum = reinterpret_cast<unsigned long long*>(q), q += kblk_b;
+        d_kboff = reinterpret_cast<unsigned long long*>(q), q += kblk_b;
+        d_E = reinterpret_cast<unsigned long long*>(q);
+        ctab.slot_of_cam = d_ctab;
+        ctab.own_cam = d_ctab + Cn;
+        ctab.nbr_cam = d_ctab + Cn + n;
+        HIP_TRY(hipMemsetAsync(d_bits, 0, 8 * (size_t)M * (size_t)Wd, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_ctab, c->h_vcam + 256, 4 * cam_tab_n, hipMemcpyHostToDevice, c->stream));
+    }
     for (long long t0 = 0; t0 < vt; t0 += per)
         hipLaunchKernelGGL(k_voxel_write, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0,
-                           d_toff, d_boff, st.at, dst, d_mult, d_sidx, d_repr);
-    if (repr)
+                           d_toff, d_boff, st.at, dst, d_mult, d_sidx, d_rank);
+    if (d_rank)
         for (long long b0 = 0; b0 < pblocks; b0 += per)
             hipLaunchKernelGGL(k_voxel_rep, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, tb, d_where,
-                               T, b0 * BLOCK, d_repr);
+                               T, b0 * BLOCK, d_rank);
     HIP_TRY(hipGetLastError());
+    if (cams) {
+        // SDM_VOXCAM_PLAIN_OR: one atomic per lane and word instead of one per run of equal rank (A/B; the same bits)
+        const bool plain_or = getenv("SDM_VOXCAM_PLAIN_OR") != nullptr;
+        const long long sper = (1ll << 31) / SUP_BLOCK;
+        for (long long b0 = 0; b0 < st.blocks; b0 += sper) {
+            const dim3 grid((unsigned)std::min(sper, st.blocks - b0));
+            if (plain_or)
+                hipLaunchKernelGGL(k_voxcam_or<false>, grid, dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
+                                   st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
+            else
+                hipLaunchKernelGGL(k_voxcam_or<true>, grid, dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
+                                   st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
+        }
+        for (long long t0 = 0; t0 < kt; t0 += per)
+            hipLaunchKernelGGL(k_voxcam_count, dim3((unsigned)std::min(per, kt - t0)), dim3(BLOCK), 0, c->stream, d_bits, Wd, M,
+                               t0, d_ktcnt);
+        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)kb), dim3(BLOCK), 0, c->stream, d_ktcnt, kt, d_ktoff, d_kbsum);
+        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_kbsum, (int)kb, d_kboff);
+        // (with no slot, k_extract_offsets writes the one entry offsets[0] = the offset of tile kt: the total)
+        hipLaunchKernelGGL(k_extract_offsets, dim3(1), dim3(BLOCK), 0, c->stream, (const ExtractSlot*)nullptr, 0, kt, d_ktoff,
+                           d_kboff, d_E);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_vcam, d_E, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the third wait: the lists' total, for the capacity check
+        const long long E = (long long)*reinterpret_cast<unsigned long long*>(c->h_vcam);
+        cams->cam_total = E;
+        if (cams->cam_slots && E > cams->cam_capacity)
+            return fail(SDM_EINVAL, "cam_capacity " + std::to_string(cams->cam_capacity) + " < " + std::to_string(E) +
+                                        " list entries (offsets, plain_total and cam_total filled)");
+        long long* d_coff = cams->cam_offsets;
+        int* d_cslots = cams->cam_slots;
+        if (!out->on_device) {
+            const size_t off_b = cams->cam_offsets ? ext_align(8 * (size_t)(M + 1)) : 0;
+            if ((rc = ext_grow_dev(&c->d_vcam_out, &c->vcam_out_bytes, off_b + (cams->cam_slots ? 4 * (size_t)E : 0)))) return rc;
+            d_coff = cams->cam_offsets ? reinterpret_cast<long long*>(c->d_vcam_out) : nullptr;
+            d_cslots = cams->cam_slots ? reinterpret_cast<int*>(c->d_vcam_out + off_b) : nullptr;
+        }
+        for (long long t0 = 0; t0 < kt; t0 += per)
+            hipLaunchKernelGGL(k_voxcam_write, dim3((unsigned)std::min(per, kt - t0)), dim3(BLOCK), 0, c->stream, d_bits, Wd, M,
+                               t0, d_ktoff, d_kboff, ctab.slot_of_cam, d_coff, d_cslots);
+        HIP_TRY(hipGetLastError());
+        if (!out->on_device) {
+            if (cams->cam_offsets)
+                HIP_TRY(hipMemcpyAsync(cams->cam_offsets, d_coff, 8 * (size_t)(M + 1), hipMemcpyDeviceToHost, c->stream));
+            if (cams->cam_slots && E > 0)
+                HIP_TRY(hipMemcpyAsync(cams->cam_slots, d_cslots, 4 * (size_t)E, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
     if (!out->on_device) {
         const size_t m = (size_t)M;
         if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, dst.xyz, 12 * m, hipMemcpyDeviceToHost, c->stream));
@@ -2501,8 +2641,23 @@ int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, do
         if (sidx) HIP_TRY(hipMemcpyAsync(sidx, d_sidx, 4 * m, hipMemcpyDeviceToHost, c->stream));
         if (repr) HIP_TRY(hipMemcpyAsync(repr, d_repr, 4 * (size_t)T, hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the third wait
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the last wait
     return SDM_OK;
+}
+
+int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
+                             float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox, long long* offsets)
+{
+    return voxel_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, voxel_size, out, vox, nullptr, offsets);
+}
+
+int sdm_extract_points_voxel_cameras(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
+                                     double max_sigma, double min_rho, float voxel_size, sdm_point_buffers* out,
+                                     sdm_voxel_buffers* vox, sdm_voxel_cameras* cams, long long* offsets)
+{
+    if (!cams) return fail(SDM_EINVAL, "null cams");
+    cams->cam_total = 0;
+    return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, offsets);
 }
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
