@@ -412,6 +412,62 @@ int sdm_extract_points_voxel_cameras(sdm_ctx *ctx, int n, const int *slots, int 
                                      int source, double max_sigma, double min_rho, float voxel_size,
                                      sdm_point_buffers *out, sdm_voxel_buffers *vox /* or NULL */,
                                      sdm_voxel_cameras *cams, long long *offsets);
+/* sdm_extract_points_voxel_cameras plus free-space evidence: per KEPT point k, crossings[k] = the number of (camera,
+ * kept point) rays of the call that pass through k's voxel on their way to another point -- the voxel-level form of the
+ * question the reference's carving asks of a (camera, point) ray.  Nothing in the reference counts it; the semantics
+ * below are this library's (tests/carve_np.py restates them in NumPy).  Every other output is, byte for byte, what
+ * sdm_extract_points_voxel_cameras returns for the same arguments.
+ * All arithmetic is IEEE binary32 without fused multiply-add and with correctly rounded division.
+ *   - Rays: one per entry of the camera lists, e in [0, E): kept point k(e) (cam_offsets[k] <= e < cam_offsets[k + 1]) and
+ *     camera slot s(e) = cam_slots[e].  The ray ends in P, the kept point's returned xyz.
+ *   - Origin: O = the camera centre of slot s from its CURRENT pose (sdm_set_pose counts), formed as the point-set pass
+ *     forms it: Rwc[i][j] = Tcw[j*4+i], Ow_i = (Rwc[i][0]*t0 + Rwc[i][1]*t1) + Rwc[i][2]*t2 with t = (Tcw[3], Tcw[7],
+ *     Tcw[11]), O = -Ow; computed on the host per distinct camera of the call.
+ *   - Cells: inv = 1.0f / voxel_size as for sdm_extract_points_voxel; cO_a = floorf(O_a * inv), cP_a = floorf(P_a * inv).
+ *     A ray is SKIPPED -- it touches nothing and adds 1 to rays_skipped -- if any of the six cells is not in
+ *     [-2^20, 2^20) (every compare is false for a NaN: an unmergeable end point or a non-finite pose skips), or if
+ *     N = sum_a |cP_a - cO_a| > max_steps.
+ *   - Walk: integer-driven, exactly N steps, ending exactly in cP.  step_a = sign(cP_a - cO_a), r_a = |cP_a - cO_a|,
+ *     d_a = P_a - O_a.  For the axes with r_a > 0: bnd_a = (float)(cO_a + (step_a > 0 ? 1 : 0)) * voxel_size,
+ *     tMax_a = (bnd_a - O_a) / d_a, tDel_a = voxel_size / fabsf(d_a).  cur = cO; for s = 0 .. N-1: cur is the ray's cell
+ *     of index s; the axis a with r_a > 0 and the smallest tMax_a is chosen -- x, y, z are scanned in turn and an axis
+ *     replaces the choice only if its tMax is strictly smaller, so ties and NaNs go to the earlier axis -- and then
+ *     cur_a += step_a, r_a -= 1, tMax_a = tMax_a + tDel_a.  Axes with r_a = 0 are never read.
+ *   - Counting: the cells of index s <= N - 1 - end_margin are counted: the camera's own cell s = 0 is, the end cell
+ *     s = N never.  For each counted cell that is the voxel of a mergeable kept point j, crossings[j] += 1.
+ *     cells_visited adds max(0, N - end_margin) per walked ray.  An unmergeable kept point has crossings 0.
+ *   - crossings and the totals are integer sums: a pure function of the arguments, the planes and the poses, bitwise the
+ *     same from run to run.  The call changes no plane, flag, list or counter beyond what
+ *     sdm_extract_points_voxel_cameras touches.
+ * `cams` follows sdm_extract_points_voxel_cameras' rules except that both of its pointers may be NULL: the lists are then
+ * formed in engine scratch and cam_capacity is ignored (cam_total is still returned).  `out` and `vox` may name no
+ * destination.  crossings follows out->on_device (4-byte aligned there) and holds out->capacity entries.
+ * Errors: every refusal of the composed calls, with its contract and in its order (offsets, plain_total and cam_total
+ * filled as there); SDM_EINVAL, checked on the host before anything is queued, also for fs == NULL, crossings == NULL,
+ * end_margin < 0, max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS and a misaligned device pointer; SDM_EINVAL for
+ * E >= 2^32.  On any refusal crossings is not written and rays_total, rays_skipped and cells_visited are 0.
+ * Cost on top of sdm_extract_points_voxel_cameras: one lane per ray; per ray a binary search in cam_offsets (at most 33
+ * 8-byte reads) and in the camera table, 12 + 16 B of end point and centre, six float divisions; per counted cell one
+ * read-only probe of the voxel table (8 B keys until the equal key or an empty slot; at load <= 0.5 a probe and a half on
+ * average) and, on a hit, 4 B of rank and one 32-bit atomic add.  The probes of one ray depend on nothing but the walk, so
+ * the pass is bound by their latency, not by bandwidth.  4 B per kept point are cleared and written (and cross the link
+ * for a host destination); two 64-bit atomics per wave carry the totals.  Engine scratch, grown on demand and freed by
+ * sdm_destroy: 16 B per distinct camera, and 12 B per kept point / 8 B per kept point / 4 B per ray for the xyz and the
+ * lists the caller names no device destination for.  No host wait beyond sdm_extract_points_voxel_cameras' four: the
+ * totals come back with the last one. */
+#define SDM_FREESPACE_MAX_STEPS 65536
+typedef struct {
+    unsigned *crossings;      /* [out->capacity] rays that traverse kept point k's voxel; follows out->on_device, 4-byte aligned; must not be NULL */
+    int end_margin;           /* in: >= 0; the last end_margin cells before the ray's end cell are not counted */
+    int max_steps;            /* in: 1 .. SDM_FREESPACE_MAX_STEPS (65536); a longer ray is skipped, not truncated */
+    long long rays_total;     /* out: E = cam_total */
+    long long rays_skipped;   /* out: rays not walked (rules above) */
+    long long cells_visited;  /* out: counted (ray, cell) pairs over all walked rays */
+} sdm_voxel_freespace;
+int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, int n_nbr, const int *nbr_slots /*[n][n_nbr]*/,
+                                       int source, double max_sigma, double min_rho, float voxel_size,
+                                       sdm_point_buffers *out, sdm_voxel_buffers *vox /* or NULL */,
+                                       sdm_voxel_cameras *cams, sdm_voxel_freespace *fs, long long *offsets);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

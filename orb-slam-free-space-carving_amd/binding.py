@@ -53,6 +53,12 @@ class VoxelCameras(C.Structure):
                 ("cam_total", C.c_longlong)]
 
 
+class VoxelFreespace(C.Structure):
+    """sdm_voxel_freespace"""
+    _fields_ = [("crossings", C.c_void_p), ("end_margin", C.c_int), ("max_steps", C.c_int), ("rays_total", C.c_longlong),
+                ("rays_skipped", C.c_longlong), ("cells_visited", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -116,6 +122,10 @@ SYMBOLS = [
     ("sdm_extract_points_voxel_cameras", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.c_float,
                                                    C.POINTER(PointBuffers), C.POINTER(VoxelBuffers),
                                                    C.POINTER(VoxelCameras), C.POINTER(C.c_longlong)]),
+    ("sdm_extract_points_voxel_freespace", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double, C.c_float,
+                                                     C.POINTER(PointBuffers), C.POINTER(VoxelBuffers),
+                                                     C.POINTER(VoxelCameras), C.POINTER(VoxelFreespace),
+                                                     C.POINTER(C.c_longlong)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -643,12 +653,31 @@ class Engine:
         nb = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(len(sl), -1)
         return self._extract_voxel(sl, nb, voxel_size, source, max_sigma, min_rho, fields, out, representative)
 
-    def _extract_voxel(self, slots, nbrs, voxel_size, source, max_sigma, min_rho, fields, out, representative, cam_entries=None):
+    def extract_points_voxel_freespace(self, slots, nbrs, voxel_size, end_margin=1, max_steps=4096, source=1, max_sigma=0.01,
+                                       min_rho=1e-6, fields=("xyz",), out=None, representative=False):
+        """extract_points_voxel_cameras plus free-space evidence (sdm_extract_points_voxel_freespace): every entry of the
+        camera lists is a ray from that camera's centre (the slot's current pose) to the kept point, walked voxel by voxel;
+        "crossings": uint32[m] counts, per kept point, the rays of the call that pass through its voxel on their way to
+        another point.  The last end_margin cells before a ray's end cell are not counted; a ray of more than max_steps
+        steps, or with a cell outside [-2**20, 2**20), is skipped.  Returns extract_points_voxel_cameras' dictionary plus
+        "crossings", "rays_total" (= cam_total), "rays_skipped" and "cells_visited".  out: as for
+        extract_points_voxel_cameras; it may also carry "crossings" (4-byte elements) -- made here for host destinations,
+        required on the device, where neither "cam_offsets" nor "cam_slots" need be given (the lists then stay in engine
+        scratch).  What to make of the counts -- e.g. keep k iff crossings[k] < its number of cameras -- is the caller's."""
+        sl = np.asarray(slots, dtype=np.int32).reshape(-1)
+        nb = np.ascontiguousarray(nbrs, dtype=np.int32).reshape(len(sl), -1)
+        return self._extract_voxel(sl, nb, voxel_size, source, max_sigma, min_rho, fields, out, representative,
+                                   fs=(int(end_margin), int(max_steps)))
+
+    def _extract_voxel(self, slots, nbrs, voxel_size, source, max_sigma, min_rho, fields, out, representative, cam_entries=None,
+                       fs=None):
         known = dict(POINT_FIELDS)
         vox_fields = {"multiplicity": (np.uint32, 1), "source_index": (np.uint32, 1), "representative": (np.uint32, 1)}
         cam_fields = {"cam_offsets": (np.int64, 1), "cam_slots": (np.int32, 1)} if nbrs is not None else {}
         known.update(vox_fields)
         known.update(cam_fields)
+        if fs is not None:
+            known["crossings"] = (np.uint32, 1)
         sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
         n = len(sl)
         given, made_slots = out, False
@@ -669,14 +698,16 @@ class Engine:
             cap = size_bound()
             out = {f: np.empty((cap, POINT_FIELDS[f][1]) if POINT_FIELDS[f][1] > 1 else (cap,), POINT_FIELDS[f][0])
                    for f in fields}
-            for f in ("multiplicity", "source_index") + (("representative",) if representative else ()):
+            for f in ("multiplicity", "source_index") + (("representative",) if representative else ()) + \
+                    (("crossings",) if fs is not None else ()):
                 out[f] = np.empty(cap, np.uint32)
         else:
             out = dict(out)
             if not any(not isinstance(a, np.ndarray) for a in out.values()):  # host: the vox outputs not given are made here
                 caps = [a.size - 1 if f == "cam_offsets" else a.size // known[f][1] for f, a in out.items()
                         if f in known and f not in ("representative", "cam_slots")]
-                need = ("multiplicity", "source_index") + (("representative",) if representative else ())
+                need = ("multiplicity", "source_index") + (("representative",) if representative else ()) + \
+                    (("crossings",) if fs is not None else ())
                 if any(f not in out for f in need):
                     bound = size_bound()
                     for f in need:
@@ -684,7 +715,9 @@ class Engine:
                             out[f] = np.empty(bound if f == "representative" or not caps else min(caps), np.uint32)
             elif representative and "representative" not in out:
                 raise ValueError('device destinations need a "representative" tensor in out')
-            elif cam_fields and not any(f in out for f in cam_fields):
+            elif fs is not None and "crossings" not in out:
+                raise ValueError('device destinations need a "crossings" tensor in out')
+            elif cam_fields and fs is None and not any(f in out for f in cam_fields):
                 raise ValueError('device destinations need a "cam_offsets" or a "cam_slots" tensor in out')
         if cam_fields and not any(not isinstance(a, np.ndarray) for a in out.values()):  # host: the lists not given are made here
             if "cam_offsets" not in out or "cam_slots" not in out:
@@ -696,7 +729,7 @@ class Engine:
                     made_slots = True
                     entries = cam_entries if cam_entries is not None else min(bound * (1 + nbrs.shape[1]), 1 << 26)
                     out["cam_slots"] = np.empty(max(entries, 1), np.int32)
-        pb, vb, vc = PointBuffers(), VoxelBuffers(), VoxelCameras()
+        pb, vb, vc, fb = PointBuffers(), VoxelBuffers(), VoxelCameras(), VoxelFreespace()
         cap, kinds = None, set()
         for f, a in out.items():
             if f not in known:
@@ -724,6 +757,8 @@ class Engine:
                 if m < 1:
                     raise ValueError("cam_offsets: need at least one entry")
                 vc.cam_offsets, m = ptr, m - 1  # (one entry more than the points)
+            elif f == "crossings":
+                fb.crossings = ptr
             else:
                 setattr(vb if f in vox_fields else pb, f, ptr)
             cap = m if cap is None else min(cap, m)
@@ -736,6 +771,12 @@ class Engine:
         if nbrs is None:
             rc = self.lib.sdm_extract_points_voxel(self.ctx, n, sl.ctypes.data_as(_ip), int(source), float(max_sigma),
                                                    float(min_rho), float(voxel_size), C.byref(pb), C.byref(vb), offp)
+        elif fs is not None:
+            fb.end_margin, fb.max_steps = fs
+            rc = self.lib.sdm_extract_points_voxel_freespace(self.ctx, n, sl.ctypes.data_as(_ip), nbrs.shape[1],
+                                                             nbrs.ctypes.data_as(_ip), int(source), float(max_sigma),
+                                                             float(min_rho), float(voxel_size), C.byref(pb), C.byref(vb),
+                                                             C.byref(vc), C.byref(fb), offp)
         else:
             rc = self.lib.sdm_extract_points_voxel_cameras(self.ctx, n, sl.ctypes.data_as(_ip), nbrs.shape[1],
                                                            nbrs.ctypes.data_as(_ip), int(source), float(max_sigma),
@@ -745,7 +786,7 @@ class Engine:
             if made_slots and cam_entries is None and int(vc.cam_total) > int(vc.cam_capacity):
                 # the cam_slots made here was too small: once more with the reported total
                 return self._extract_voxel(slots, nbrs, voxel_size, source, max_sigma, min_rho, fields, given, representative,
-                                           cam_entries=int(vc.cam_total))
+                                           cam_entries=int(vc.cam_total), fs=fs)
             e = SdmError(rc, self.lib.sdm_last_error().decode())
             e.offsets = offs
             e.plain_total = int(vb.plain_total)
@@ -761,6 +802,9 @@ class Engine:
         res["plain_total"] = plain
         if nbrs is not None:
             res["cam_total"] = int(vc.cam_total)
+        if fs is not None:
+            res["rays_total"], res["rays_skipped"] = int(fb.rays_total), int(fb.rays_skipped)
+            res["cells_visited"] = int(fb.cells_visited)
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):

@@ -33,6 +33,7 @@
 #include "sdm_covis.h"
 #include "sdm_voxel.h"
 #include "sdm_voxcam.h"
+#include "sdm_carve.h"
 
 using namespace sdm;
 
@@ -255,6 +256,10 @@ struct sdm_ctx {
     size_t vcam_out_bytes = 0;
     unsigned char* h_vcam = nullptr;
     size_t vcam_host_bytes = 0;
+    // sdm_extract_points_voxel_freespace (sdm_carve.h): the camera centres, the two call totals, and the kept points' xyz
+    // when no destination holds them on the device (lists and counters without one go to d_vcam_out); grows on demand
+    unsigned char* d_carve = nullptr;
+    size_t carve_bytes = 0;
 
     // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
     ObsStore obs{};                 // obs.cap != 0 once allocated
@@ -1111,6 +1116,7 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->d_vox_out);
     (void)hipFree(c->d_vcam);
     (void)hipFree(c->d_vcam_out);
+    (void)hipFree(c->d_carve);
     (void)hipHostFree(c->h_vcam);
     (void)hipHostFree(c->h_ext);
     (void)hipFree(c->obs.ids);
@@ -2379,20 +2385,22 @@ int sdm_extract_points_support(sdm_ctx* c, int n, const int* slots, int n_nbr, c
 }
 
 // ---- one point per voxel (sdm_extract_points_voxel, sdm_voxel.h; with `cams` sdm_extract_points_voxel_cameras,
-// sdm_voxcam.h: the neighbour table is read only then) -----------------------------------------------------------------
+// sdm_voxcam.h: the neighbour table is read only then; with `fs` also sdm_extract_points_voxel_freespace, sdm_carve.h:
+// the lists and the kept points' xyz are then formed on the device whether the caller takes them or not) -----------------
 static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
                       double min_rho, float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox,
-                      sdm_voxel_cameras* cams, long long* offsets)
+                      sdm_voxel_cameras* cams, sdm_voxel_freespace* fs, long long* offsets)
 {
     if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
     if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
     if (cams) {
         if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
-        if (!cams->cam_offsets && !cams->cam_slots) return fail(SDM_EINVAL, "no camera output requested");
+        if (!fs && !cams->cam_offsets && !cams->cam_slots) return fail(SDM_EINVAL, "no camera output requested");
         if (cams->cam_slots && cams->cam_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
         if (out->on_device && ((uintptr_t)cams->cam_offsets % 8 || (uintptr_t)cams->cam_slots % 4))
             return fail(SDM_EINVAL, "device buffer not aligned (cam_offsets: 8 B; cam_slots: 4 B)");
     }
+    if (fs && out->on_device && (uintptr_t)fs->crossings % 4) return fail(SDM_EINVAL, "device buffer not aligned (crossings: 4 B)");
     if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(SDM_EINVAL, "voxel_size must be finite and > 0");
     const float inv = 1.0f / voxel_size;
     if (!std::isfinite(inv)) return fail(SDM_EINVAL, "1 / voxel_size is not finite");
@@ -2495,12 +2503,26 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
         for (int s = 0; s < c->cfg.max_keyframes; s++)
             if (cam_of[(size_t)s] == 0) cam_of[(size_t)s] = Cn++;
         cam_tab_n = (size_t)Cn + (size_t)n + np;
-        if ((rc = ext_grow_host(&c->h_vcam, &c->vcam_host_bytes, 256 + 4 * cam_tab_n))) return rc;
+        if ((rc = ext_grow_host(&c->h_vcam, &c->vcam_host_bytes, 256 + ext_align(4 * cam_tab_n) + (fs ? 16 * (size_t)Cn : 0))))
+            return rc;
         int* h_tab = reinterpret_cast<int*>(c->h_vcam + 256);
         for (int s = 0; s < c->cfg.max_keyframes; s++)
             if (cam_of[(size_t)s] >= 0) h_tab[cam_of[(size_t)s]] = s;
         for (int i = 0; i < n; i++) h_tab[Cn + i] = cam_of[(size_t)slots[i]];
         for (size_t i = 0; i < np; i++) h_tab[(size_t)Cn + (size_t)n + i] = cam_of[(size_t)nbr_slots[i]];
+        if (fs) {  // the camera centres from the current poses, as pointset_pixel forms Ow: O = -(Rwc * tcw)
+            float* h_org = reinterpret_cast<float*>(c->h_vcam + 256 + ext_align(4 * cam_tab_n));
+            for (int q = 0; q < Cn; q++) {
+                const float* Tcw = c->h_meta[h_tab[q]].Tcw;
+                float Rwc[9], Ow[3];
+                const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
+                for (int i = 0; i < 3; i++)
+                    for (int k = 0; k < 3; k++) Rwc[i * 3 + k] = Tcw[k * 4 + i];
+                mat3_vec(Rwc, tcw, Ow);
+                for (int i = 0; i < 3; i++) h_org[q * 4 + i] = -Ow[i];
+                h_org[q * 4 + 3] = 0.f;
+            }
+        }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the kept total sizes what follows
     if (h_voffs[n + 1]) return fail(SDM_EHIP, "voxel table overflow");
@@ -2540,6 +2562,16 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
         d_sidx = sidx ? reinterpret_cast<unsigned*>(b + sidx_off) : nullptr;
         d_repr = repr ? reinterpret_cast<unsigned*>(b + repr_off) : nullptr;
     }
+    // (fs) the centres, the call totals, and the kept points' xyz when no destination holds them on the device
+    float* d_org = nullptr;
+    unsigned long long* d_fs_tot = nullptr;
+    if (fs) {
+        const size_t org_b = ext_align(16 * (size_t)Cn), xyz_at = org_b + 256;
+        if ((rc = ext_grow_dev(&c->d_carve, &c->carve_bytes, xyz_at + (dst.xyz ? 0 : 12 * (size_t)M)))) return rc;
+        d_org = reinterpret_cast<float*>(c->d_carve);
+        d_fs_tot = reinterpret_cast<unsigned long long*>(c->d_carve + org_b);
+        if (!dst.xyz) dst.xyz = reinterpret_cast<float*>(c->d_carve + xyz_at);
+    }
     // (cams) scratch: the staged camera table, every plain point's kept rank when the caller takes no `representative`,
     // the bitsets, the tile counts and their scan; grown before anything that reads it is queued
     unsigned* d_rank = d_repr;
@@ -2574,6 +2606,9 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
         ctab.nbr_cam = d_ctab + Cn + n;
         HIP_TRY(hipMemsetAsync(d_bits, 0, 8 * (size_t)M * (size_t)Wd, c->stream));
         HIP_TRY(hipMemcpyAsync(d_ctab, c->h_vcam + 256, 4 * cam_tab_n, hipMemcpyHostToDevice, c->stream));
+        if (fs)
+            HIP_TRY(hipMemcpyAsync(d_org, c->h_vcam + 256 + ext_align(4 * cam_tab_n), 16 * (size_t)Cn, hipMemcpyHostToDevice,
+                                   c->stream));
     }
     for (long long t0 = 0; t0 < vt; t0 += per)
         hipLaunchKernelGGL(k_voxel_write, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0,
@@ -2612,18 +2647,53 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
         if (cams->cam_slots && E > cams->cam_capacity)
             return fail(SDM_EINVAL, "cam_capacity " + std::to_string(cams->cam_capacity) + " < " + std::to_string(E) +
                                         " list entries (offsets, plain_total and cam_total filled)");
+        if (fs && E >= (1ll << 32)) return fail(SDM_EINVAL, "2^32 or more rays in one call");
         long long* d_coff = cams->cam_offsets;
         int* d_cslots = cams->cam_slots;
-        if (!out->on_device) {
-            const size_t off_b = cams->cam_offsets ? ext_align(8 * (size_t)(M + 1)) : 0;
-            if ((rc = ext_grow_dev(&c->d_vcam_out, &c->vcam_out_bytes, off_b + (cams->cam_slots ? 4 * (size_t)E : 0)))) return rc;
-            d_coff = cams->cam_offsets ? reinterpret_cast<long long*>(c->d_vcam_out) : nullptr;
-            d_cslots = cams->cam_slots ? reinterpret_cast<int*>(c->d_vcam_out + off_b) : nullptr;
+        unsigned* d_cross = fs ? fs->crossings : nullptr;
+        if (!out->on_device || fs) {
+            // on the device: the caller's arrays, and with fs whatever of the lists it did not name; else a staging region
+            // per requested output (with fs: both lists and the counters)
+            const bool s_off = fs ? !(out->on_device && cams->cam_offsets) : cams->cam_offsets != nullptr;
+            const bool s_slots = fs ? !(out->on_device && cams->cam_slots) : cams->cam_slots != nullptr;
+            const size_t off_b = s_off ? ext_align(8 * (size_t)(M + 1)) : 0;
+            const size_t slots_b = s_slots ? ext_align(4 * (size_t)E) : 0;
+            const size_t cross_b = (fs && !out->on_device) ? 4 * (size_t)M : 0;
+            if ((rc = ext_grow_dev(&c->d_vcam_out, &c->vcam_out_bytes, off_b + slots_b + cross_b))) return rc;
+            if (s_off) d_coff = reinterpret_cast<long long*>(c->d_vcam_out);
+            else if (!out->on_device) d_coff = nullptr;
+            if (s_slots) d_cslots = reinterpret_cast<int*>(c->d_vcam_out + off_b);
+            else if (!out->on_device) d_cslots = nullptr;
+            if (cross_b) d_cross = reinterpret_cast<unsigned*>(c->d_vcam_out + off_b + slots_b);
         }
         for (long long t0 = 0; t0 < kt; t0 += per)
             hipLaunchKernelGGL(k_voxcam_write, dim3((unsigned)std::min(per, kt - t0)), dim3(BLOCK), 0, c->stream, d_bits, Wd, M,
                                t0, d_ktoff, d_kboff, ctab.slot_of_cam, d_coff, d_cslots);
         HIP_TRY(hipGetLastError());
+        if (fs) {  // sdm_carve.h: one lane per list entry walks its ray through the table
+            HIP_TRY(hipMemsetAsync(d_cross, 0, 4 * (size_t)M, c->stream));
+            HIP_TRY(hipMemsetAsync(d_fs_tot, 0, 16, c->stream));
+            CarveIn in;
+            in.xyz = dst.xyz;
+            in.cam_offsets = d_coff;
+            in.cam_slots = d_cslots;
+            in.slot_of_cam = ctab.slot_of_cam;
+            in.origin = d_org;
+            in.M = M;
+            in.E = E;
+            in.Cn = Cn;
+            in.voxel = voxel_size;
+            in.inv = inv;
+            in.end_margin = fs->end_margin;
+            in.max_steps = fs->max_steps;
+            const long long eblocks = (E + BLOCK - 1) / BLOCK;
+            for (long long b0 = 0; b0 < eblocks; b0 += per)
+                hipLaunchKernelGGL(k_voxel_carve, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in,
+                                   b0 * BLOCK, tb, d_cross, d_fs_tot);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c->h_vcam + 16, d_fs_tot, 16, hipMemcpyDeviceToHost, c->stream));
+            if (!out->on_device) HIP_TRY(hipMemcpyAsync(fs->crossings, d_cross, 4 * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+        }
         if (!out->on_device) {
             if (cams->cam_offsets)
                 HIP_TRY(hipMemcpyAsync(cams->cam_offsets, d_coff, 8 * (size_t)(M + 1), hipMemcpyDeviceToHost, c->stream));
@@ -2642,13 +2712,19 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
         if (repr) HIP_TRY(hipMemcpyAsync(repr, d_repr, 4 * (size_t)T, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));  // the last wait
+    if (fs) {
+        const unsigned long long* tot = reinterpret_cast<const unsigned long long*>(c->h_vcam + 16);
+        fs->rays_total = cams->cam_total;
+        fs->rays_skipped = (long long)tot[0];
+        fs->cells_visited = (long long)tot[1];
+    }
     return SDM_OK;
 }
 
 int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
                              float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox, long long* offsets)
 {
-    return voxel_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, voxel_size, out, vox, nullptr, offsets);
+    return voxel_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, voxel_size, out, vox, nullptr, nullptr, offsets);
 }
 
 int sdm_extract_points_voxel_cameras(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
@@ -2657,7 +2733,23 @@ int sdm_extract_points_voxel_cameras(sdm_ctx* c, int n, const int* slots, int n_
 {
     if (!cams) return fail(SDM_EINVAL, "null cams");
     cams->cam_total = 0;
-    return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, offsets);
+    return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, nullptr, offsets);
+}
+
+int sdm_extract_points_voxel_freespace(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
+                                       double max_sigma, double min_rho, float voxel_size, sdm_point_buffers* out,
+                                       sdm_voxel_buffers* vox, sdm_voxel_cameras* cams, sdm_voxel_freespace* fs,
+                                       long long* offsets)
+{
+    if (fs) fs->rays_total = fs->rays_skipped = fs->cells_visited = 0;
+    if (!cams) return fail(SDM_EINVAL, "null cams");
+    cams->cam_total = 0;
+    if (!fs) return fail(SDM_EINVAL, "null fs");
+    if (!fs->crossings) return fail(SDM_EINVAL, "null crossings");
+    if (fs->end_margin < 0) return fail(SDM_EINVAL, "negative end_margin");
+    if (fs->max_steps < 1 || fs->max_steps > SDM_FREESPACE_MAX_STEPS)
+        return fail(SDM_EINVAL, "max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS");
+    return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, fs, offsets);
 }
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
