@@ -468,6 +468,102 @@ int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, in
                                        int source, double max_sigma, double min_rho, float voxel_size,
                                        sdm_point_buffers *out, sdm_voxel_buffers *vox /* or NULL */,
                                        sdm_voxel_cameras *cams, sdm_voxel_freespace *fs, long long *offsets);
+/* ---- the persistent voxel map ------------------------------------------------------------------------ */
+/* sdm_extract_points_voxel merges within one call.  The voxel map keeps the merge in the context ACROSS calls: each
+ * sdm_vmap_integrate merges the plain cloud of its slots into the entries left by the calls before it and reports exactly
+ * what changed, so an online consumer (one keyframe or one block per call) appends the created entries and rewrites the
+ * updated ones without re-reading the cloud.  Nothing in the reference does this; the semantics below are this library's
+ * and make the map a pure function of the sequence of calls (tests/vmap_np.py restates them in NumPy).
+ * One map per context, optional.  voxel_size, inv = 1.0f / voxel_size, the cell floorf(xyz_k * inv), mergeability (all
+ * three cells in [-2^20, 2^20), every compare false for a NaN) and key(sigma) are exactly sdm_extract_points_voxel's.
+ *   - State: entries id = 0 .. M-1, one per distinct voxel ever seen.  An entry carries the record of its winning point
+ *     -- xyz, pixel, rho_sigma, intensity as sdm_extract_points returns them, and tag (int) -- plus multiplicity (u32)
+ *     and epoch (u32, the number of the call whose point is the winner).  Counters: points, dropped, calls, rehashes.
+ *   - Integrating: call number c counts the successful sdm_vmap_integrate calls since open or clear, from 1.  Its plain
+ *     cloud g = 0 .. T-1 is what sdm_extract_points returns for (n, slots, source, max_sigma, min_rho) on the state at
+ *     the time of the call, in its order; xyz is the point-set plane as stored.  A point's tag is tags[i] for its slot
+ *     slots[i], or the slot number when tags == NULL (slots are recycled in an online run: pass the keyframe ids).
+ *     The result is defined as if the points were processed one by one in increasing g:
+ *       * an unmergeable point adds 1 to `dropped` and is not stored (the one deliberate difference from the per-call
+ *         merge, which keeps such points: a voxel map has no voxel for them);
+ *       * a point whose voxel has no entry creates entry id = M: its record is the point, multiplicity = 1, epoch = c;
+ *         then M += 1;
+ *       * otherwise multiplicity += 1, saturating at 2^32 - 1, and if key(sigma_g) < the key of the entry's stored
+ *         sigma, STRICTLY, the record becomes the point and epoch = c.
+ *     `points` adds the mergeable points (a 64-bit sum).
+ *     So an entry's winner minimises (key(sigma), G) over the concatenation G of all integrated plain clouds in call
+ *     order: the smallest sigma wins, ties go to the earlier call, then the earlier slot, then raster order.  Ids are the
+ *     order of each voxel's FIRST point in G: append-only, they never change.
+ *   - Delta of call c: first_created = M before the call; created = entries appended, with ids first_created ..
+ *     first_created + created - 1; updated = entries with id < first_created whose epoch became c; updated_ids lists
+ *     those ids in ascending order of the plain index g of the entry's final winner in this call; plain_total = T;
+ *     dropped = this call's dropped points.
+ *   - Invariants: integrating slots s0 .. sk in one call, in k+1 calls of one slot, or in any split into consecutive
+ *     groups leaves a byte-identical map except `epoch` and `calls`.  One call into an empty map gives, matched by
+ *     (tag, pixel), exactly the mergeable kept points of sdm_extract_points_voxel for the same arguments, with the same
+ *     field bits and multiplicities, and `dropped` = its unmergeable kept points.  Integrating the same slots again
+ *     with unchanged planes gives created = 0, updated = 0 and doubles every multiplicity.
+ * Everything is integer or copied bits: every returned array is bitwise the same from run to run.
+ * sdm_vmap_open: reserve_voxels sizes the table (the power of two >= 2 x reserve_voxels, at least 1024 slots) and the
+ * records; 0 = the minimum.  sdm_vmap_clear: an empty map as after open (all counters 0), the capacity kept.
+ * sdm_vmap_close frees the map; sdm_destroy does too.
+ * sdm_vmap_fetch returns entries first .. first + count - 1 when ids == NULL, else entries ids[0 .. count) (first must
+ * be 0 then).  ids and the pointers of `extra` follow out->on_device and are 4-byte aligned there (rho_sigma: 8).  Any
+ * pointer of `out` and `extra` may be NULL, and so may `extra`; at least one destination must be named.
+ * sdm_point_buffers keeps its layout.
+ * Errors, all raised before the map changes (a refused call leaves sdm_vmap_get_info and a full fetch as they were):
+ *   SDM_ESTATE: no open map; open on an open map; a context without with_pointset; the slot states sdm_extract_points
+ *     refuses.
+ *   SDM_EINVAL: sdm_extract_points' argument errors; a voxel_size sdm_extract_points_voxel refuses; negative
+ *     reserve_voxels (or more than 2^30); a misaligned device pointer; updated_ids != NULL with updated_capacity <
+ *     min(M, T), the a-priori bound on `updated` (plain_total and first_created are filled); M + T > 2^30 (the table would
+ *     pass 2^31 slots); fetch: count < 0, count > out->capacity, a range beyond M, an id >= M (device ids: a kernel flag
+ *     read at the final wait; the destinations are then unspecified), first != 0 with ids, no destination.
+ *   SDM_EHIP: an allocation failure while growing -- growth is done before anything is inserted.
+ * Changes no plane, flag, list or counter of the engine, and uses scratch of its own: interleaved
+ * sdm_extract_points_voxel* calls are undisturbed.
+ * Cost per sdm_vmap_integrate, outside a growth proportional to T and not to M or the table: sdm_extract_points' passes
+ * with all four fields staged (25 B per plain point); per plain point one probe of the table with four integer atomics
+ * (a 64-bit compare-and-swap, a 64-bit min, a 32-bit min, a 32-bit add) and 4 B of table position; three more passes over
+ * those 4 B and the table fields; per created or updated entry a 37 B record.  Growth: when 2 (M + T) exceeds the table's
+ * slots a table of the next sufficient power of two is made and every old slot re-inserted (`rehashes` counts these);
+ * the records grow geometrically by device copies.  Memory: 28 B per table slot, 37 B per record.  Three host waits: T,
+ * the counts, the end.  sdm_vmap_fetch: one copy per field of exactly count elements (range form), after one gather
+ * launch (ids form).
+ * Limits: a keyframe's contribution cannot be removed; stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
+ * integrate the resident slots again); no camera lists or free-space evidence on the persistent map; one rank only. */
+typedef struct {
+    long long voxels;       /* M */
+    long long points;       /* mergeable points integrated */
+    long long dropped;      /* unmergeable points met */
+    long long calls;        /* successful sdm_vmap_integrate calls since open / clear */
+    long long table_slots;
+    long long rehashes;     /* table growths since open / clear */
+    float voxel_size;
+} sdm_vmap_info;
+typedef struct {
+    unsigned *updated_ids;        /* in: [updated_capacity] or NULL */
+    long long updated_capacity;   /* in */
+    int on_device;                /* in: 1: updated_ids is device memory of this context's GPU (4-byte aligned) */
+    long long plain_total;        /* out: T */
+    long long dropped;            /* out */
+    long long first_created;      /* out: M before the call */
+    long long created;            /* out */
+    long long updated;            /* out */
+} sdm_vmap_delta;
+typedef struct {
+    int *tag;                 /* [out->capacity] or NULL */
+    unsigned *multiplicity;   /* [out->capacity] or NULL */
+    unsigned *epoch;          /* [out->capacity] or NULL */
+} sdm_vmap_fields;
+int sdm_vmap_open(sdm_ctx *ctx, float voxel_size, long long reserve_voxels);
+int sdm_vmap_clear(sdm_ctx *ctx);
+int sdm_vmap_close(sdm_ctx *ctx);
+int sdm_vmap_get_info(sdm_ctx *ctx, sdm_vmap_info *info);
+int sdm_vmap_integrate(sdm_ctx *ctx, int n, const int *slots, const int *tags /*[n] or NULL*/, int source,
+                       double max_sigma, double min_rho, sdm_vmap_delta *delta /* or NULL */);
+int sdm_vmap_fetch(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
+                   sdm_point_buffers *out, sdm_vmap_fields *extra /* or NULL */);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

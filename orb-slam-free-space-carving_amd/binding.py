@@ -59,6 +59,24 @@ class VoxelFreespace(C.Structure):
                 ("rays_skipped", C.c_longlong), ("cells_visited", C.c_longlong)]
 
 
+class VmapInfo(C.Structure):
+    """sdm_vmap_info"""
+    _fields_ = [("voxels", C.c_longlong), ("points", C.c_longlong), ("dropped", C.c_longlong), ("calls", C.c_longlong),
+                ("table_slots", C.c_longlong), ("rehashes", C.c_longlong), ("voxel_size", C.c_float)]
+
+
+class VmapDelta(C.Structure):
+    """sdm_vmap_delta"""
+    _fields_ = [("updated_ids", C.c_void_p), ("updated_capacity", C.c_longlong), ("on_device", C.c_int),
+                ("plain_total", C.c_longlong), ("dropped", C.c_longlong), ("first_created", C.c_longlong),
+                ("created", C.c_longlong), ("updated", C.c_longlong)]
+
+
+class VmapFields(C.Structure):
+    """sdm_vmap_fields"""
+    _fields_ = [("tag", C.c_void_p), ("multiplicity", C.c_void_p), ("epoch", C.c_void_p)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -69,6 +87,10 @@ def lib_path():
 
 
 _lib = None
+
+# sdm_vmap_fetch fields beyond the point fields
+VMAP_EXTRA_FIELDS = {"tag": (np.int32, 1), "multiplicity": (np.uint32, 1), "epoch": (np.uint32, 1)}
+VMAP_FIELDS = tuple(POINT_FIELDS) + tuple(VMAP_EXTRA_FIELDS)
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -126,6 +148,13 @@ SYMBOLS = [
                                                      C.POINTER(PointBuffers), C.POINTER(VoxelBuffers),
                                                      C.POINTER(VoxelCameras), C.POINTER(VoxelFreespace),
                                                      C.POINTER(C.c_longlong)]),
+    ("sdm_vmap_open", C.c_int, [_ctx, C.c_float, C.c_longlong]),
+    ("sdm_vmap_clear", C.c_int, [_ctx]),
+    ("sdm_vmap_close", C.c_int, [_ctx]),
+    ("sdm_vmap_get_info", C.c_int, [_ctx, C.POINTER(VmapInfo)]),
+    ("sdm_vmap_integrate", C.c_int, [_ctx, C.c_int, _ip, _ip, C.c_int, C.c_double, C.c_double, C.POINTER(VmapDelta)]),
+    ("sdm_vmap_fetch", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(PointBuffers),
+                                 C.POINTER(VmapFields)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -806,6 +835,120 @@ class Engine:
             res["rays_total"], res["rays_skipped"] = int(fb.rays_total), int(fb.rays_skipped)
             res["cells_visited"] = int(fb.cells_visited)
         return res
+
+    # -- the persistent voxel map ------------------------------------------------------------------
+    def vmap_open(self, voxel_size, reserve_voxels=0):
+        """opens the context's voxel map (sdm_vmap_open): one entry per voxel of edge voxel_size, merged across calls"""
+        self._check(self.lib.sdm_vmap_open(self.ctx, float(voxel_size), int(reserve_voxels)))
+
+    def vmap_clear(self):
+        """an empty map as after vmap_open, the capacity kept (sdm_vmap_clear)"""
+        self._check(self.lib.sdm_vmap_clear(self.ctx))
+
+    def vmap_close(self):
+        self._check(self.lib.sdm_vmap_close(self.ctx))
+
+    def vmap_info(self):
+        """{"voxels", "points", "dropped", "calls", "table_slots", "rehashes", "voxel_size"} (sdm_vmap_get_info)"""
+        info = VmapInfo()
+        self._check(self.lib.sdm_vmap_get_info(self.ctx, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in VmapInfo._fields_}
+
+    def _dest(self, name, a, dt, per, kinds, align=None):
+        """(address, elements / per) of a destination: a C-contiguous NumPy array or a torch tensor on this engine's device"""
+        if isinstance(a, np.ndarray):
+            if a.dtype != dt or not a.flags.c_contiguous or a.size % per:
+                raise ValueError("%s: need a C-contiguous %s array of [m, %d]" % (name, np.dtype(dt).name, per))
+            kinds.add("host")
+            return a.ctypes.data, a.size // per
+        if not (getattr(a, "is_cuda", False) and a.is_contiguous()) or a.element_size() != np.dtype(dt).itemsize:
+            raise ValueError("%s: need a contiguous device tensor of %d-byte elements" % (name, np.dtype(dt).itemsize))
+        if a.get_device() != self.device:
+            raise ValueError("%s: tensor on device %d, engine on device %d" % (name, a.get_device(), self.device))
+        kinds.add("device")
+        if a.data_ptr() % (align or np.dtype(dt).itemsize):
+            raise ValueError("%s: device tensor address not %d-byte aligned" % (name, align or np.dtype(dt).itemsize))
+        return a.data_ptr(), a.numel() // per
+
+    def vmap_integrate(self, slots, tags=None, source=1, max_sigma=0.01, min_rho=1e-6, updated=True):
+        """Merges the plain cloud of `slots` (what extract_points returns for the same arguments) into the voxel map
+        (sdm_vmap_integrate); tags[i] is stored with the points of slots[i] (default: the slot numbers).  Returns the
+        call's delta {"plain_total", "dropped", "first_created", "created", "updated"}: the created entries have the ids
+        first_created .. first_created + created - 1, and "updated_ids" (uint32[updated]) lists the older entries whose
+        point was replaced.  updated: True -- an array is made here; False -- the ids are not returned; or the
+        destination, a uint32 array (pageable, or pinned from host_alloc) or a torch device tensor of 4-byte elements.
+        A refusal raises SdmError with .plain_total and .first_created."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        n = len(sl)
+        tp = None
+        if tags is not None:
+            tg = np.ascontiguousarray(np.asarray(tags, dtype=np.int32).reshape(-1))
+            if len(tg) != n:
+                raise ValueError("tags: need one per slot")
+            tp = tg.ctypes.data_as(_ip)
+        d = VmapDelta()
+        dest = None
+        if updated is True:
+            bound = min(self.vmap_info()["voxels"], self.extract_bound(sl, source, min_rho))
+            dest = np.empty(max(bound, 1), np.uint32)
+        elif updated is not False and updated is not None:
+            dest = updated
+        if dest is not None:
+            kinds = set()
+            d.updated_ids, d.updated_capacity = self._dest("updated_ids", dest, np.uint32, 1, kinds)
+            d.on_device = 1 if kinds == {"device"} else 0
+        rc = self.lib.sdm_vmap_integrate(self.ctx, n, sl.ctypes.data_as(_ip), tp, int(source), float(max_sigma),
+                                         float(min_rho), C.byref(d))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.plain_total, e.first_created = int(d.plain_total), int(d.first_created)
+            raise e
+        res = {f: int(getattr(d, f)) for f in ("plain_total", "dropped", "first_created", "created", "updated")}
+        if dest is not None:
+            res["updated_ids"] = dest[:res["updated"]]
+        return res
+
+    def vmap_fetch(self, ids=None, first=0, count=None, fields=VMAP_FIELDS, out=None):
+        """Entries of the voxel map (sdm_vmap_fetch): first .. first + count - 1 (count None: to the end), or the entries
+        ids[...] (a uint32 array, or a torch device tensor of 4-byte elements together with device destinations in out).
+        fields: any of xyz, pixel, rho_sigma, intensity (as extract_points), tag int32[m], multiplicity uint32[m],
+        epoch uint32[m].  out: {field: preallocated array} under extract_points' rules.  Returns {field: array}."""
+        known = dict(POINT_FIELDS)
+        known.update(VMAP_EXTRA_FIELDS)
+        kinds = set()
+        idp = None
+        if ids is not None:
+            if isinstance(ids, np.ndarray) or not getattr(ids, "is_cuda", False):
+                ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+            idp, nid = self._dest("ids", ids, np.uint32, 1, kinds)
+            if count is None:
+                count = nid
+            elif count > nid:
+                raise ValueError("ids: fewer than count")
+        elif count is None:
+            count = max(self.vmap_info()["voxels"] - int(first), 0)
+        if out is None:
+            if kinds == {"device"}:
+                raise ValueError("device ids need device destinations in out")
+            for f in fields:
+                if f not in known:
+                    raise ValueError("unknown voxel map field %r" % (f,))
+            cap = max(int(count), 1)
+            out = {f: np.empty((cap, known[f][1]) if known[f][1] > 1 else (cap,), known[f][0]) for f in fields}
+        pb, vf = PointBuffers(), VmapFields()
+        cap = None
+        for f, a in out.items():
+            if f not in known:
+                raise ValueError("unknown voxel map field %r" % (f,))
+            ptr, m = self._dest(f, a, known[f][0], known[f][1], kinds, 8 if f == "rho_sigma" else None)
+            setattr(vf if f in VMAP_EXTRA_FIELDS else pb, f, ptr)
+            cap = m if cap is None else min(cap, m)
+        if len(kinds) > 1:
+            raise ValueError("ids and out mix host arrays and device tensors")
+        pb.capacity = cap if cap is not None else 0
+        pb.on_device = 1 if kinds == {"device"} else 0
+        self._check(self.lib.sdm_vmap_fetch(self.ctx, idp, int(first), int(count), C.byref(pb), C.byref(vf)))
+        return {f: a[:count] if known[f][1] == 1 else a.reshape(-1, known[f][1])[:count] for f, a in out.items()}
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

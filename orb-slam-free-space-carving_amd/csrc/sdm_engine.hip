@@ -34,6 +34,7 @@
 #include "sdm_voxel.h"
 #include "sdm_voxcam.h"
 #include "sdm_carve.h"
+#include "sdm_vmap.h"
 
 using namespace sdm;
 
@@ -260,6 +261,26 @@ struct sdm_ctx {
     // when no destination holds them on the device (lists and counters without one go to d_vcam_out); grows on demand
     unsigned char* d_carve = nullptr;
     size_t carve_bytes = 0;
+    // the persistent voxel map (sdm_vmap_*, sdm_vmap.h): the table and the records live from open to close; the per-call
+    // scratch (where[], tile counts and offsets, tags, counters), the staging of host destinations and the pinned mirror
+    // of tags and totals are the map's own and grow on demand
+    struct Vmap {
+        bool open = false;
+        float voxel_size = 0.f, inv = 0.f;
+        long long M = 0, points = 0, dropped = 0, calls = 0, rehashes = 0;
+        unsigned long long cap = 0;     // table slots
+        unsigned char* d_table = nullptr;
+        VmapTable tb{};
+        long long rec_cap = 0;          // entries the records hold
+        unsigned char* d_rec = nullptr;
+        VmapRecords rec{};
+        unsigned char* d_scratch = nullptr;
+        size_t scratch_bytes = 0;
+        unsigned char* d_out = nullptr;
+        size_t out_bytes = 0;
+        unsigned char* h_pin = nullptr;
+        size_t pin_bytes = 0;
+    } vmap;
 
     // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
     ObsStore obs{};                 // obs.cap != 0 once allocated
@@ -1117,6 +1138,11 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->d_vcam);
     (void)hipFree(c->d_vcam_out);
     (void)hipFree(c->d_carve);
+    (void)hipFree(c->vmap.d_table);
+    (void)hipFree(c->vmap.d_rec);
+    (void)hipFree(c->vmap.d_scratch);
+    (void)hipFree(c->vmap.d_out);
+    (void)hipHostFree(c->vmap.h_pin);
     (void)hipHostFree(c->h_vcam);
     (void)hipHostFree(c->h_ext);
     (void)hipFree(c->obs.ids);
@@ -2750,6 +2776,387 @@ int sdm_extract_points_voxel_freespace(sdm_ctx* c, int n, const int* slots, int 
     if (fs->max_steps < 1 || fs->max_steps > SDM_FREESPACE_MAX_STEPS)
         return fail(SDM_EINVAL, "max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS");
     return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, fs, offsets);
+}
+
+// ---- the persistent voxel map (sdm_vmap_*, sdm_vmap.h) -------------------------------------------------------------------
+// one block for the table: keys | cval | id | cfirst | ccnt (28 B per slot), set to empty keys / the reductions' identities
+static int vmap_make_table(sdm_ctx* c, unsigned long long cap, unsigned char** block, VmapTable* tb)
+{
+    const size_t n = (size_t)cap;
+    HIP_TRY(hipMalloc((void**)block, 28 * n));
+    unsigned char* p = *block;
+    tb->keys = reinterpret_cast<unsigned long long*>(p);
+    tb->cval = reinterpret_cast<unsigned long long*>(p + 8 * n);
+    tb->id = reinterpret_cast<unsigned*>(p + 16 * n);
+    tb->cfirst = reinterpret_cast<unsigned*>(p + 20 * n);
+    tb->ccnt = reinterpret_cast<unsigned*>(p + 24 * n);
+    tb->mask = cap - 1;
+    hipError_t e = hipMemsetAsync(p, 0xff, 24 * n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p + 24 * n, 0, 4 * n, c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(*block);
+        *block = nullptr;
+        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    return SDM_OK;
+}
+
+// one block for the records of `cap` entries, every array 256-byte aligned
+static int vmap_make_records(long long cap, unsigned char** block, VmapRecords* r)
+{
+    const size_t n = (size_t)std::max(cap, 1ll);
+    const size_t b4 = ext_align(4 * n);
+    HIP_TRY(hipMalloc((void**)block, ext_align(12 * n) + ext_align(8 * n) + 4 * b4 + ext_align(n)));
+    unsigned char* p = *block;
+    r->xyz = reinterpret_cast<float*>(p), p += ext_align(12 * n);
+    r->rho_sigma = reinterpret_cast<float2*>(p), p += ext_align(8 * n);
+    r->pixel = reinterpret_cast<unsigned*>(p), p += b4;
+    r->tag = reinterpret_cast<int*>(p), p += b4;
+    r->multiplicity = reinterpret_cast<unsigned*>(p), p += b4;
+    r->epoch = reinterpret_cast<unsigned*>(p), p += b4;
+    r->intensity = p;
+    return SDM_OK;
+}
+
+static void vmap_free(sdm_ctx* c)
+{
+    sdm_ctx::Vmap& v = c->vmap;
+    (void)hipFree(v.d_table);
+    (void)hipFree(v.d_rec);
+    (void)hipFree(v.d_scratch);
+    (void)hipFree(v.d_out);
+    (void)hipHostFree(v.h_pin);
+    v = sdm_ctx::Vmap{};
+}
+
+int sdm_vmap_open(sdm_ctx* c, float voxel_size, long long reserve_voxels)
+{
+    if (!c) return fail(SDM_EINVAL, "null argument");
+    if (c->vmap.open) return fail(SDM_ESTATE, "the context already has an open voxel map");
+    if (!c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
+    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(SDM_EINVAL, "voxel_size must be finite and > 0");
+    const float inv = 1.0f / voxel_size;
+    if (!std::isfinite(inv)) return fail(SDM_EINVAL, "1 / voxel_size is not finite");
+    if (reserve_voxels < 0 || reserve_voxels > (1ll << 30)) return fail(SDM_EINVAL, "reserve_voxels outside 0 .. 2^30");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    sdm_ctx::Vmap& v = c->vmap;
+    unsigned long long cap = 1024;
+    while (cap < 2ull * (unsigned long long)reserve_voxels) cap <<= 1;
+    int rc;
+    if ((rc = vmap_make_table(c, cap, &v.d_table, &v.tb)) || (rc = vmap_make_records(reserve_voxels, &v.d_rec, &v.rec))) {
+        vmap_free(c);
+        return rc;
+    }
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        vmap_free(c);
+        return fail(SDM_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    v.cap = cap;
+    v.rec_cap = std::max(reserve_voxels, 1ll);
+    v.voxel_size = voxel_size;
+    v.inv = inv;
+    v.open = true;
+    return SDM_OK;
+}
+
+int sdm_vmap_clear(sdm_ctx* c)
+{
+    if (!c) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
+    HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    v.M = v.points = v.dropped = v.calls = v.rehashes = 0;
+    return SDM_OK;
+}
+
+int sdm_vmap_close(sdm_ctx* c)
+{
+    if (!c) return fail(SDM_EINVAL, "null argument");
+    if (!c->vmap.open) return fail(SDM_ESTATE, "no open voxel map");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    vmap_free(c);
+    return SDM_OK;
+}
+
+int sdm_vmap_get_info(sdm_ctx* c, sdm_vmap_info* info)
+{
+    if (!c || !info) return fail(SDM_EINVAL, "null argument");
+    const sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    std::memset(info, 0, sizeof(*info));
+    info->voxels = v.M;
+    info->points = v.points;
+    info->dropped = v.dropped;
+    info->calls = v.calls;
+    info->table_slots = (long long)v.cap;
+    info->rehashes = v.rehashes;
+    info->voxel_size = v.voxel_size;
+    return SDM_OK;
+}
+
+// table and records for `need` entries, made before anything is inserted; the old ones stay intact if an allocation fails
+static int vmap_grow(sdm_ctx* c, long long need)
+{
+    sdm_ctx::Vmap& v = c->vmap;
+    int rc;
+    if (2ull * (unsigned long long)need > v.cap) {
+        unsigned long long cap = v.cap;
+        while (cap < 2ull * (unsigned long long)need) cap <<= 1;
+        unsigned char* block = nullptr;
+        VmapTable nw{};
+        if ((rc = vmap_make_table(c, cap, &block, &nw))) return rc;
+        HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 8, c->stream));  // (the counters: the caller has sized the scratch)
+        const unsigned long long per = 1ull << 31;  // work-items of one dispatch
+        for (unsigned long long h0 = 0; h0 < v.cap; h0 += per)
+            hipLaunchKernelGGL(k_vmap_rehash, dim3((unsigned)((std::min(per, v.cap - h0) + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                               c->stream, v.tb.keys, v.tb.id, v.cap, h0, nw, reinterpret_cast<unsigned*>(v.d_scratch));
+        unsigned* h_ctr = reinterpret_cast<unsigned*>(v.h_pin);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_ctr, v.d_scratch, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || h_ctr[1]) {
+            (void)hipFree(block);
+            return fail(SDM_EHIP, e != hipSuccess ? std::string("voxel map rehash: ") + hipGetErrorString(e)
+                                                  : std::string("voxel map table overflow while rehashing"));
+        }
+        (void)hipFree(v.d_table);
+        v.d_table = block;
+        v.tb = nw;
+        v.cap = cap;
+        v.rehashes++;
+    }
+    if (need > v.rec_cap) {
+        const long long cap = std::max(need, 2 * v.rec_cap);  // geometric: the copies amortise
+        unsigned char* block = nullptr;
+        VmapRecords nr{};
+        if ((rc = vmap_make_records(cap, &block, &nr))) return rc;
+        const size_t m = (size_t)v.M;
+        hipError_t e = hipSuccess;
+        if (m) {
+            e = hipMemcpyAsync(nr.xyz, v.rec.xyz, 12 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nr.rho_sigma, v.rec.rho_sigma, 8 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nr.pixel, v.rec.pixel, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nr.tag, v.rec.tag, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nr.multiplicity, v.rec.multiplicity, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nr.epoch, v.rec.epoch, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nr.intensity, v.rec.intensity, m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+        if (e != hipSuccess) {
+            (void)hipFree(block);
+            return fail(SDM_EHIP, std::string("voxel map records: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(v.d_rec);
+        v.d_rec = block;
+        v.rec = nr;
+        v.rec_cap = cap;
+    }
+    return SDM_OK;
+}
+
+int sdm_vmap_integrate(sdm_ctx* c, int n, const int* slots, const int* tags, int source, double max_sigma, double min_rho,
+                       sdm_vmap_delta* delta)
+{
+    if (delta) delta->plain_total = delta->dropped = delta->first_created = delta->created = delta->updated = 0;
+    if (!c) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
+    unsigned* upd_dst = delta ? delta->updated_ids : nullptr;
+    if (upd_dst && delta->updated_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
+    if (upd_dst && delta->on_device && (uintptr_t)upd_dst % 4) return fail(SDM_EINVAL, "device buffer not aligned (updated_ids: 4 B)");
+
+    // the plain cloud, all four fields, into the engine's staging
+    ExtractStaged st{};
+    st.pixel = st.intensity = true;
+    sdm_point_buffers none{};
+    std::vector<long long> plain((size_t)n + 1, 0);
+    int rc = extract_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
+    if (rc) return rc;
+    const long long T = st.total;
+    if (delta) delta->plain_total = T, delta->first_created = v.M;
+    if (v.M + T > (1ll << 30)) return fail(SDM_EINVAL, "more than 2^30 entries and plain points: the voxel map's table would exceed 2^31 slots");
+    if (upd_dst && delta->updated_capacity < std::min(v.M, T))
+        return fail(SDM_EINVAL, "updated_capacity " + std::to_string(delta->updated_capacity) + " < min(entries, plain points) = " +
+                                    std::to_string(std::min(v.M, T)) + " (plain_total and first_created filled)");
+    if (T == 0) {  // (extract_core has waited for the stream)
+        v.calls++;
+        return SDM_OK;
+    }
+
+    // scratch, staging and growth: everything is allocated before anything is inserted
+    const long long vt = (T + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t where_b = ext_align(4 * (size_t)T), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
+    const size_t blk_b = ext_align(8 * (size_t)vb), tag_b = ext_align(4 * (size_t)n);
+    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + where_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b + tag_b))) return rc;
+    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tag_b))) return rc;
+    const bool stage_upd = upd_dst && !delta->on_device;
+    if (stage_upd && (rc = ext_grow_dev(&v.d_out, &v.out_bytes, 4 * (size_t)std::min(v.M, T)))) return rc;
+    if ((rc = vmap_grow(c, v.M + T))) return rc;
+    unsigned char* p = v.d_scratch;
+    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                           // {dropped, overflow}
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, updated, dropped, overflow}
+    p += 512;
+    unsigned* d_where = reinterpret_cast<unsigned*>(p);
+    p += where_b;
+    unsigned* d_cnt_new = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_cnt_upd = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off_new = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned* d_off_upd = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum_new = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_new = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_bsum_upd = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_upd = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    int* d_tags = reinterpret_cast<int*>(p);
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
+    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
+    for (int i = 0; i < n; i++) h_tags[i] = tags ? tags[i] : slots[i];
+
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, 8, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_tags, h_tags, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long pblocks = (T + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vmap_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, st.at.xyz,
+                           st.at.rho_sigma, T, b0 * BLOCK, v.inv, v.tb, d_where, d_ctr);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where, T,
+                           t0, d_cnt_new, d_cnt_upd);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_new, vt, d_off_new, d_bsum_new);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_new, (int)vb, d_boff_new);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_upd, vt, d_off_upd, d_bsum_upd);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_upd, (int)vb, d_boff_upd);
+    hipLaunchKernelGGL(k_vmap_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_new, d_boff_new, d_off_upd, d_boff_upd, d_ctr,
+                       d_tot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: created and updated
+    if (h_tot[3]) return fail(SDM_EHIP, "voxel map table overflow");
+    const long long created = (long long)h_tot[0], updated = (long long)h_tot[1], dropped = (long long)h_tot[2];
+
+    unsigned* d_upd = !upd_dst ? nullptr : stage_upd ? reinterpret_cast<unsigned*>(v.d_out) : upd_dst;
+    const unsigned first_created = (unsigned)v.M, epoch = (unsigned)(v.calls + 1);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_ids, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
+                           first_created, T, t0, d_off_new, d_boff_new);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
+                           first_created, epoch, T, t0, d_off_upd, d_boff_upd, st.at, st.d_offsets, d_tags, n, d_upd);
+    HIP_TRY(hipGetLastError());
+    if (stage_upd && updated)
+        HIP_TRY(hipMemcpyAsync(upd_dst, d_upd, 4 * (size_t)updated, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    v.M += created;
+    v.points += T - dropped;
+    v.dropped += dropped;
+    v.calls++;
+    if (delta) delta->created = created, delta->updated = updated, delta->dropped = dropped;
+    return SDM_OK;
+}
+
+int sdm_vmap_fetch(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_point_buffers* out,
+                   sdm_vmap_fields* extra)
+{
+    if (!c || !out) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    int* tag = extra ? extra->tag : nullptr;
+    unsigned* mult = extra ? extra->multiplicity : nullptr;
+    unsigned* epoch = extra ? extra->epoch : nullptr;
+    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity && !tag && !mult && !epoch)
+        return fail(SDM_EINVAL, "no output requested");
+    if (count < 0 || out->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
+    if (count > out->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
+    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
+        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
+    const bool dev = out->on_device != 0;
+    if (dev && (((uintptr_t)out->xyz | (uintptr_t)out->pixel | (uintptr_t)tag | (uintptr_t)mult | (uintptr_t)epoch | (uintptr_t)ids) % 4 ||
+                (uintptr_t)out->rho_sigma % 8))
+        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel, tag, multiplicity, epoch, ids: 4 B; rho_sigma: 8 B)");
+    if (ids && !dev)
+        for (long long j = 0; j < count; j++)
+            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (count == 0) return SDM_OK;
+    const size_t m = (size_t)count;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    VmapRecords src = v.rec;
+    unsigned* h_bad = nullptr;
+    if (!ids) {
+        const size_t f = (size_t)first;
+        src.xyz += 3 * f, src.pixel += f, src.rho_sigma += f, src.intensity += f, src.tag += f, src.multiplicity += f, src.epoch += f;
+    } else {
+        // ids, the flag and -- for host destinations -- one dense region per requested field
+        size_t at = ext_align(4 * m) + 256;
+        size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, tag_off = 0, mult_off = 0, ep_off = 0;
+        if (!dev) {
+            if (out->xyz) xyz_off = at, at += ext_align(12 * m);
+            if (out->pixel) pix_off = at, at += ext_align(4 * m);
+            if (out->rho_sigma) rs_off = at, at += ext_align(8 * m);
+            if (out->intensity) im_off = at, at += ext_align(m);
+            if (tag) tag_off = at, at += ext_align(4 * m);
+            if (mult) mult_off = at, at += ext_align(4 * m);
+            if (epoch) ep_off = at, at += ext_align(4 * m);
+        }
+        int rc;
+        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, at)) || (rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256))) return rc;
+        unsigned char* b = v.d_out;
+        const unsigned* d_ids = ids;
+        unsigned* d_bad = reinterpret_cast<unsigned*>(b + ext_align(4 * m));
+        h_bad = reinterpret_cast<unsigned*>(v.h_pin);
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(b, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
+            d_ids = reinterpret_cast<const unsigned*>(b);
+        }
+        VmapRecords dst{};
+        if (dev) {
+            dst.xyz = out->xyz, dst.pixel = out->pixel, dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
+            dst.intensity = out->intensity, dst.tag = tag, dst.multiplicity = mult, dst.epoch = epoch;
+        } else {
+            dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
+            dst.pixel = out->pixel ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
+            dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
+            dst.intensity = out->intensity ? b + im_off : nullptr;
+            dst.tag = tag ? reinterpret_cast<int*>(b + tag_off) : nullptr;
+            dst.multiplicity = mult ? reinterpret_cast<unsigned*>(b + mult_off) : nullptr;
+            dst.epoch = epoch ? reinterpret_cast<unsigned*>(b + ep_off) : nullptr;
+        }
+        HIP_TRY(hipMemsetAsync(d_bad, 0, 4, c->stream));
+        const long long per = (1ll << 31) / BLOCK;
+        const long long blocks = (count + BLOCK - 1) / BLOCK;
+        for (long long b0 = 0; b0 < blocks; b0 += per)
+            hipLaunchKernelGGL(k_vmap_gather, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, v.rec, d_ids,
+                               count, b0 * BLOCK, (unsigned)v.M, dst, d_bad);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+        src = dst;
+    }
+    if (!ids || !dev) {  // one copy per field of exactly count elements
+        if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, src.xyz, 12 * m, kind, c->stream));
+        if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, src.pixel, 4 * m, kind, c->stream));
+        if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, src.rho_sigma, 8 * m, kind, c->stream));
+        if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, src.intensity, m, kind, c->stream));
+        if (tag) HIP_TRY(hipMemcpyAsync(tag, src.tag, 4 * m, kind, c->stream));
+        if (mult) HIP_TRY(hipMemcpyAsync(mult, src.multiplicity, 4 * m, kind, c->stream));
+        if (epoch) HIP_TRY(hipMemcpyAsync(epoch, src.epoch, 4 * m, kind, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
+    return SDM_OK;
 }
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
