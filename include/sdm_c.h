@@ -531,7 +531,8 @@ int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, in
  * the counts, the end.  sdm_vmap_fetch: one copy per field of exactly count elements (range form), after one gather
  * launch (ids form).
  * Limits: a keyframe's contribution cannot be removed; stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
- * integrate the resident slots again); no camera lists or free-space evidence on the persistent map; one rank only. */
+ * integrate the resident slots again); free-space evidence is kept per entry by sdm_vmap_carve (below), camera lists on
+ * the persistent map remain later work; one rank only. */
 typedef struct {
     long long voxels;       /* M */
     long long points;       /* mergeable points integrated */
@@ -564,6 +565,68 @@ int sdm_vmap_integrate(sdm_ctx *ctx, int n, const int *slots, const int *tags /*
                        double max_sigma, double min_rho, sdm_vmap_delta *delta /* or NULL */);
 int sdm_vmap_fetch(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
                    sdm_point_buffers *out, sdm_vmap_fields *extra /* or NULL */);
+/* Free-space evidence on the persistent map: the (camera, point) rays of a call are walked through the map's table on
+ * the device and counted per ENTRY, so an online caller integrates a finished block, carves it, and fetches the counters by
+ * id like every other field.  Nothing in the reference counts this; the semantics below are this library's
+ * (tests/vmap_carve_np.py restates them in NumPy).
+ *   - State: every entry carries two 64-bit counters, crossings and ends.  Both are 0 when the entry is created;
+ *     sdm_vmap_clear puts both back to 0.  (64 bits: the voxel at a camera centre collects every ray of that camera, and
+ *     no realistic sequence wraps them.)
+ *   - Plain cloud: sdm_vmap_carve reads the plain cloud g = 0 .. T-1 of (n, slots, source, max_sigma, min_rho) exactly as
+ *     sdm_vmap_integrate does.
+ *   - Cameras of a point: with n_nbr >= 1 it also reads the support words of sdm_extract_points_support for the same
+ *     arguments; C(g) = {slots[i(g)]} U {nbr_slots[i(g)][j] : bit j of support[g]}, i(g) the index of the point's slot.
+ *     C(g) is a SET: a repeated neighbour and a neighbour equal to the point's own slot fall out.  n_nbr == 0 with
+ *     nbr_slots == NULL is allowed: C(g) is then the observing slot alone and no support pass runs.
+ *   - Rays: one per (g, s in C(g)), from O, the camera centre of slot s from its CURRENT pose -- formed on the host
+ *     exactly as sdm_extract_points_voxel_freespace forms it, once per distinct camera of the call -- to P, the plain
+ *     point's own staged xyz (not the entry's record).  The skip rule, the cells, the integer-driven walk of exactly N
+ *     steps, the tie rule and the counted cells s <= N - 1 - end_margin are sdm_extract_points_voxel_freespace's, word for
+ *     word, with the map's voxel_size and inv.  A non-finite or out-of-range point or centre skips its ray.
+ *   - Counting: for every counted cell whose key has an entry, crossings[id] += 1.  For every walked (not skipped) ray
+ *     whose end cell cP has an entry, ends[id] += 1, whatever end_margin.
+ *   - The map is read, not changed: nothing is inserted; no id, record, multiplicity, epoch or counter of
+ *     sdm_vmap_get_info changes.  Evidence is therefore relative to the entries present at the call: integrate a block,
+ *     then carve it.
+ *   - Everything is an integer sum: the counters and totals are bitwise the same from run to run, whatever the table
+ *     layout.  For a fixed map carving is additive over any split or order of the slots into calls.  The counters survive
+ *     table rehashes and record growth; entries created later start at 0.
+ * sdm_vmap_fetch_evidence follows the range and ids forms of sdm_vmap_fetch (ids follow ev->on_device, 4-byte aligned
+ * there; crossings and ends 8-byte aligned); it returns zeros if no carve has run; at least one destination must be named.
+ * Errors, all raised before any counter changes: SDM_ESTATE for no open map and the slot and neighbour states
+ * sdm_extract_points and sdm_extract_points_support refuse; SDM_EINVAL for their argument errors, cv == NULL,
+ * end_margin < 0, max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS, n_nbr < 0, n_nbr > max_neighbours, n_nbr == 0 with a
+ * table and n_nbr >= 1 without one, and the fetch errors exactly as sdm_vmap_fetch (range beyond M, count > capacity, an
+ * id >= M, first != 0 with ids, a misaligned device pointer, no destination); SDM_EHIP for an allocation failure --
+ * everything is allocated before anything is counted.  On a refusal the outs of cv are 0, except plain_total once known.
+ * Cost: sdm_extract_points' passes (20 B per plain point staged) and, with neighbours, sdm_extract_points_support's pass;
+ * one lane per candidate (g, d), d = 0 .. D, D = the most distinct neighbours of one slot; per live ray six float
+ * divisions and per counted cell one read-only probe of the table (8 B keys; on a hit 4 B of id and one 64-bit atomic
+ * add), plus one probe for the end cell.  The probes of a ray depend on the walk alone: the pass is bound by their latency.
+ * Memory: 16 B per record of capacity, allocated at the first carve.  Two host waits: T, the end (with the totals).
+ * Limits: evidence is relative to the entries present at each carve, so -- unlike the map itself -- it is NOT invariant
+ * under re-splitting integrates and carves against each other; carving the same slots twice counts twice; the counters go
+ * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed; one rank only. */
+typedef struct {
+    int end_margin;            /* in: >= 0 */
+    int max_steps;             /* in: 1 .. SDM_FREESPACE_MAX_STEPS */
+    long long plain_total;     /* out: T */
+    long long rays_total;      /* out */
+    long long rays_skipped;    /* out */
+    long long cells_visited;   /* out: counted (ray, cell) pairs */
+    long long cells_hit;       /* out: of those, cells that hold an entry = sum of the crossings added */
+    long long ends_hit;        /* out: walked rays whose end cell holds an entry = sum of the ends added */
+} sdm_vmap_carve_args;
+typedef struct {
+    unsigned long long *crossings;  /* [capacity] or NULL */
+    unsigned long long *ends;       /* [capacity] or NULL */
+    long long capacity;
+    int on_device;                  /* pointers (and ids) are device memory, 8-byte aligned (ids: 4) */
+} sdm_vmap_evidence;
+int sdm_vmap_carve(sdm_ctx *ctx, int n, const int *slots, int n_nbr, const int *nbr_slots /*[n][n_nbr] or NULL*/,
+                   int source, double max_sigma, double min_rho, sdm_vmap_carve_args *cv);
+int sdm_vmap_fetch_evidence(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
+                            sdm_vmap_evidence *ev);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -77,6 +77,18 @@ class VmapFields(C.Structure):
     _fields_ = [("tag", C.c_void_p), ("multiplicity", C.c_void_p), ("epoch", C.c_void_p)]
 
 
+class VmapCarveArgs(C.Structure):
+    """sdm_vmap_carve_args"""
+    _fields_ = [("end_margin", C.c_int), ("max_steps", C.c_int), ("plain_total", C.c_longlong), ("rays_total", C.c_longlong),
+                ("rays_skipped", C.c_longlong), ("cells_visited", C.c_longlong), ("cells_hit", C.c_longlong),
+                ("ends_hit", C.c_longlong)]
+
+
+class VmapEvidence(C.Structure):
+    """sdm_vmap_evidence"""
+    _fields_ = [("crossings", C.c_void_p), ("ends", C.c_void_p), ("capacity", C.c_longlong), ("on_device", C.c_int)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -91,6 +103,9 @@ _lib = None
 # sdm_vmap_fetch fields beyond the point fields
 VMAP_EXTRA_FIELDS = {"tag": (np.int32, 1), "multiplicity": (np.uint32, 1), "epoch": (np.uint32, 1)}
 VMAP_FIELDS = tuple(POINT_FIELDS) + tuple(VMAP_EXTRA_FIELDS)
+# sdm_vmap_fetch_evidence fields, and the outs of sdm_vmap_carve
+VMAP_EVIDENCE_FIELDS = ("crossings", "ends")
+VMAP_CARVE_OUTS = ("plain_total", "rays_total", "rays_skipped", "cells_visited", "cells_hit", "ends_hit")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -155,6 +170,9 @@ SYMBOLS = [
     ("sdm_vmap_integrate", C.c_int, [_ctx, C.c_int, _ip, _ip, C.c_int, C.c_double, C.c_double, C.POINTER(VmapDelta)]),
     ("sdm_vmap_fetch", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(PointBuffers),
                                  C.POINTER(VmapFields)]),
+    ("sdm_vmap_carve", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double,
+                                 C.POINTER(VmapCarveArgs)]),
+    ("sdm_vmap_fetch_evidence", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(VmapEvidence)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -949,6 +967,69 @@ class Engine:
         pb.on_device = 1 if kinds == {"device"} else 0
         self._check(self.lib.sdm_vmap_fetch(self.ctx, idp, int(first), int(count), C.byref(pb), C.byref(vf)))
         return {f: a[:count] if known[f][1] == 1 else a.reshape(-1, known[f][1])[:count] for f, a in out.items()}
+
+    def vmap_carve(self, slots, nbrs=None, end_margin=1, max_steps=4096, source=1, max_sigma=0.01, min_rho=1e-6):
+        """Free-space evidence on the voxel map (sdm_vmap_carve): walks the rays from the cameras of every plain point of
+        `slots` -- the observing slot and, with nbrs int32[n, n_nbr], the neighbours that confirm it as
+        extract_points_support reports them -- to the point through the map and adds, per entry, the rays that cross its
+        voxel (`crossings`) and the rays that end in it (`ends`).  The map itself is only read: integrate a block, then
+        carve it.  Returns {"plain_total", "rays_total", "rays_skipped", "cells_visited", "cells_hit", "ends_hit"}.  A
+        refusal raises SdmError with .plain_total."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        n = len(sl)
+        n_nbr, nbp = 0, None
+        if nbrs is not None:
+            nb = np.ascontiguousarray(np.asarray(nbrs, dtype=np.int32))
+            if nb.ndim != 2 or nb.shape[0] != n:
+                raise ValueError("nbrs: need int32[n, n_nbr], one row per slot")
+            n_nbr, nbp = nb.shape[1], nb.ctypes.data_as(_ip)
+        cv = VmapCarveArgs()
+        cv.end_margin, cv.max_steps = int(end_margin), int(max_steps)
+        rc = self.lib.sdm_vmap_carve(self.ctx, n, sl.ctypes.data_as(_ip), n_nbr, nbp, int(source), float(max_sigma),
+                                     float(min_rho), C.byref(cv))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.plain_total = int(cv.plain_total)
+            raise e
+        return {f: int(getattr(cv, f)) for f in VMAP_CARVE_OUTS}
+
+    def vmap_fetch_evidence(self, ids=None, first=0, count=None, fields=VMAP_EVIDENCE_FIELDS, out=None):
+        """The free-space counters of the voxel map's entries (sdm_vmap_fetch_evidence), selected as vmap_fetch selects:
+        crossings uint64[m] and ends uint64[m]; zeros before the first vmap_carve.  out: {field: preallocated uint64
+        array (pageable, or pinned from host_alloc) or torch device tensor of 8-byte elements (int64: view it)}."""
+        kinds = set()
+        idp = None
+        if ids is not None:
+            if isinstance(ids, np.ndarray) or not getattr(ids, "is_cuda", False):
+                ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+            idp, nid = self._dest("ids", ids, np.uint32, 1, kinds)
+            if count is None:
+                count = nid
+            elif count > nid:
+                raise ValueError("ids: fewer than count")
+        elif count is None:
+            count = max(self.vmap_info()["voxels"] - int(first), 0)
+        if out is None:
+            if kinds == {"device"}:
+                raise ValueError("device ids need device destinations in out")
+            for f in fields:
+                if f not in VMAP_EVIDENCE_FIELDS:
+                    raise ValueError("unknown evidence field %r" % (f,))
+            out = {f: np.empty(max(int(count), 1), np.uint64) for f in fields}
+        ev = VmapEvidence()
+        cap = None
+        for f, a in out.items():
+            if f not in VMAP_EVIDENCE_FIELDS:
+                raise ValueError("unknown evidence field %r" % (f,))
+            ptr, m = self._dest(f, a, np.uint64, 1, kinds)
+            setattr(ev, f, ptr)
+            cap = m if cap is None else min(cap, m)
+        if len(kinds) > 1:
+            raise ValueError("ids and out mix host arrays and device tensors")
+        ev.capacity = cap if cap is not None else 0
+        ev.on_device = 1 if kinds == {"device"} else 0
+        self._check(self.lib.sdm_vmap_fetch_evidence(self.ctx, idp, int(first), int(count), C.byref(ev)))
+        return {f: a[:count] for f, a in out.items()}
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

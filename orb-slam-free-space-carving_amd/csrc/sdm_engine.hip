@@ -35,6 +35,7 @@
 #include "sdm_voxcam.h"
 #include "sdm_carve.h"
 #include "sdm_vmap.h"
+#include "sdm_vmap_carve.h"
 
 using namespace sdm;
 
@@ -263,7 +264,8 @@ struct sdm_ctx {
     size_t carve_bytes = 0;
     // the persistent voxel map (sdm_vmap_*, sdm_vmap.h): the table and the records live from open to close; the per-call
     // scratch (where[], tile counts and offsets, tags, counters), the staging of host destinations and the pinned mirror
-    // of tags and totals are the map's own and grow on demand
+    // of tags and totals are the map's own and grow on demand.  The free-space counters (sdm_vmap_carve, sdm_vmap_carve.h) are
+    // an allocation of their own beside the records: made at the first carve for rec_cap entries, grown with the records
     struct Vmap {
         bool open = false;
         float voxel_size = 0.f, inv = 0.f;
@@ -274,6 +276,8 @@ struct sdm_ctx {
         long long rec_cap = 0;          // entries the records hold
         unsigned char* d_rec = nullptr;
         VmapRecords rec{};
+        unsigned char* d_evid = nullptr;  // crossings[rec_cap] | ends[rec_cap], or null before the first carve
+        unsigned long long *crossings = nullptr, *ends = nullptr;
         unsigned char* d_scratch = nullptr;
         size_t scratch_bytes = 0;
         unsigned char* d_out = nullptr;
@@ -1140,6 +1144,7 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->d_carve);
     (void)hipFree(c->vmap.d_table);
     (void)hipFree(c->vmap.d_rec);
+    (void)hipFree(c->vmap.d_evid);
     (void)hipFree(c->vmap.d_scratch);
     (void)hipFree(c->vmap.d_out);
     (void)hipHostFree(c->vmap.h_pin);
@@ -2818,11 +2823,29 @@ static int vmap_make_records(long long cap, unsigned char** block, VmapRecords* 
     return SDM_OK;
 }
 
+// one block for the free-space counters of `cap` entries: crossings | ends, both zero
+static int vmap_make_evidence(sdm_ctx* c, long long cap, unsigned char** block, unsigned long long** crossings,
+                              unsigned long long** ends)
+{
+    const size_t b8 = ext_align(8 * (size_t)std::max(cap, 1ll));
+    HIP_TRY(hipMalloc((void**)block, 2 * b8));
+    *crossings = reinterpret_cast<unsigned long long*>(*block);
+    *ends = reinterpret_cast<unsigned long long*>(*block + b8);
+    const hipError_t e = hipMemsetAsync(*block, 0, 2 * b8, c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(*block);
+        *block = nullptr;
+        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    return SDM_OK;
+}
+
 static void vmap_free(sdm_ctx* c)
 {
     sdm_ctx::Vmap& v = c->vmap;
     (void)hipFree(v.d_table);
     (void)hipFree(v.d_rec);
+    (void)hipFree(v.d_evid);
     (void)hipFree(v.d_scratch);
     (void)hipFree(v.d_out);
     (void)hipHostFree(v.h_pin);
@@ -2868,6 +2891,7 @@ int sdm_vmap_clear(sdm_ctx* c)
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
     HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
+    if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, 2 * ext_align(8 * (size_t)v.rec_cap), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     v.M = v.points = v.dropped = v.calls = v.rehashes = 0;
     return SDM_OK;
@@ -2935,9 +2959,20 @@ static int vmap_grow(sdm_ctx* c, long long need)
         unsigned char* block = nullptr;
         VmapRecords nr{};
         if ((rc = vmap_make_records(cap, &block, &nr))) return rc;
+        unsigned char* evid = nullptr;  // the free-space counters grow with the records: M entries copied, the rest zero
+        unsigned long long *ncr = nullptr, *nen = nullptr;
+        if (v.d_evid && (rc = vmap_make_evidence(c, cap, &evid, &ncr, &nen))) {
+            (void)hipFree(block);
+            return rc;
+        }
         const size_t m = (size_t)v.M;
         hipError_t e = hipSuccess;
-        if (m) {
+        if (evid) {
+            if (m) e = hipMemcpyAsync(ncr, v.crossings, 8 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (m && e == hipSuccess) e = hipMemcpyAsync(nen, v.ends, 8 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
+        }
+        if (m && e == hipSuccess) {
             e = hipMemcpyAsync(nr.xyz, v.rec.xyz, 12 * m, hipMemcpyDeviceToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(nr.rho_sigma, v.rec.rho_sigma, 8 * m, hipMemcpyDeviceToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(nr.pixel, v.rec.pixel, 4 * m, hipMemcpyDeviceToDevice, c->stream);
@@ -2949,7 +2984,14 @@ static int vmap_grow(sdm_ctx* c, long long need)
         }
         if (e != hipSuccess) {
             (void)hipFree(block);
+            (void)hipFree(evid);
             return fail(SDM_EHIP, std::string("voxel map records: ") + hipGetErrorString(e));
+        }
+        if (evid) {  // (waited for above, as the records are)
+            (void)hipFree(v.d_evid);
+            v.d_evid = evid;
+            v.crossings = ncr;
+            v.ends = nen;
         }
         (void)hipFree(v.d_rec);
         v.d_rec = block;
@@ -3153,6 +3195,194 @@ int sdm_vmap_fetch(sdm_ctx* c, const unsigned* ids, long long first, long long c
         if (tag) HIP_TRY(hipMemcpyAsync(tag, src.tag, 4 * m, kind, c->stream));
         if (mult) HIP_TRY(hipMemcpyAsync(mult, src.multiplicity, 4 * m, kind, c->stream));
         if (epoch) HIP_TRY(hipMemcpyAsync(epoch, src.epoch, 4 * m, kind, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
+    return SDM_OK;
+}
+
+// ---- free-space evidence on the persistent voxel map (sdm_vmap_carve.h) --------------------------------------------------
+int sdm_vmap_carve(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
+                   double min_rho, sdm_vmap_carve_args* cv)
+{
+    if (cv) cv->plain_total = cv->rays_total = cv->rays_skipped = cv->cells_visited = cv->cells_hit = cv->ends_hit = 0;
+    if (!c || !cv) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
+    if (cv->end_margin < 0) return fail(SDM_EINVAL, "negative end_margin");
+    if (cv->max_steps < 1 || cv->max_steps > SDM_FREESPACE_MAX_STEPS)
+        return fail(SDM_EINVAL, "max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS");
+    if (n_nbr < 0) return fail(SDM_EINVAL, "negative n_nbr");
+    if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
+    if ((n_nbr == 0) != (nbr_slots == nullptr))
+        return fail(SDM_EINVAL, n_nbr ? "null nbr_slots" : "n_nbr == 0 with a neighbour table");
+
+    // the plain cloud (xyz and rho_sigma) and, with neighbours, the support words into the engine's staging
+    ExtractStaged st{};
+    st.support = n_nbr > 0;
+    sdm_point_buffers none{};
+    std::vector<long long> plain((size_t)n + 1, 0);
+    int rc = extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
+    if (rc) return rc;
+    const long long T = st.total;
+    cv->plain_total = T;
+    if (T == 0) return SDM_OK;  // (extract_core has waited for the stream)
+
+    // the cameras of the call: its distinct slots in ascending order, and per slot i the distinct neighbours other than
+    // slots[i], in the order of their first column, each with the mask of the columns that name it (extract_core has
+    // checked every slot's range; n_nbr <= 64)
+    std::vector<int> cam_of((size_t)c->cfg.max_keyframes, -1);
+    for (int i = 0; i < n; i++) cam_of[(size_t)slots[i]] = 0;
+    for (size_t i = 0; i < (size_t)n * (size_t)n_nbr; i++) cam_of[(size_t)nbr_slots[i]] = 0;
+    int Cn = 0;
+    std::vector<int> slot_of_cam;
+    for (int s = 0; s < c->cfg.max_keyframes; s++)
+        if (cam_of[(size_t)s] == 0) cam_of[(size_t)s] = Cn++, slot_of_cam.push_back(s);
+    std::vector<std::vector<std::pair<int, unsigned long long>>> lists((size_t)n);
+    int D = 0;
+    for (int i = 0; i < n; i++) {
+        auto& l = lists[(size_t)i];
+        for (int j = 0; j < n_nbr; j++) {
+            const int s = nbr_slots[(size_t)i * (size_t)n_nbr + (size_t)j];
+            if (s == slots[i]) continue;
+            size_t k = 0;
+            while (k < l.size() && l[k].first != s) k++;
+            if (k == l.size()) l.emplace_back(s, 0ull);
+            l[k].second |= 1ull << j;
+        }
+        D = std::max(D, (int)l.size());
+    }
+
+    // the counters, the scratch and the pinned mirror: everything is allocated before anything is counted
+    if (!v.d_evid && (rc = vmap_make_evidence(c, v.rec_cap, &v.d_evid, &v.crossings, &v.ends))) return rc;
+    const size_t nd = (size_t)n * (size_t)D;
+    const size_t org_b = ext_align(16 * (size_t)Cn), own_b = ext_align(4 * (size_t)n), cam_b = ext_align(4 * nd),
+                 mask_b = ext_align(8 * nd), tab_b = org_b + own_b + cam_b + mask_b;
+    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + tab_b))) return rc;
+    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tab_b))) return rc;
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(v.d_scratch + 256);
+    unsigned char* d_tab = v.d_scratch + 512;
+    unsigned char* h_tab = v.h_pin + 256;
+    float* h_org = reinterpret_cast<float*>(h_tab);
+    int* h_own = reinterpret_cast<int*>(h_tab + org_b);
+    int* h_cam = reinterpret_cast<int*>(h_tab + org_b + own_b);
+    unsigned long long* h_mask = reinterpret_cast<unsigned long long*>(h_tab + org_b + own_b + cam_b);
+    for (int q = 0; q < Cn; q++) {  // the camera centres from the current poses, as pointset_pixel forms Ow: O = -(Rwc * tcw)
+        const float* Tcw = c->h_meta[slot_of_cam[(size_t)q]].Tcw;
+        float Rwc[9], Ow[3];
+        const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
+        for (int i = 0; i < 3; i++)
+            for (int k = 0; k < 3; k++) Rwc[i * 3 + k] = Tcw[k * 4 + i];
+        mat3_vec(Rwc, tcw, Ow);
+        for (int i = 0; i < 3; i++) h_org[q * 4 + i] = -Ow[i];
+        h_org[q * 4 + 3] = 0.f;
+    }
+    for (int i = 0; i < n; i++) {
+        h_own[i] = cam_of[(size_t)slots[i]];
+        const auto& l = lists[(size_t)i];
+        for (int d = 0; d < D; d++) {
+            const bool have = (size_t)d < l.size();
+            h_cam[(size_t)i * (size_t)D + (size_t)d] = have ? cam_of[(size_t)l[(size_t)d].first] : 0;
+            h_mask[(size_t)i * (size_t)D + (size_t)d] = have ? l[(size_t)d].second : 0ull;
+        }
+    }
+    HIP_TRY(hipMemsetAsync(d_tot, 0, 64, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_b, hipMemcpyHostToDevice, c->stream));
+    VmapCarveIn in;
+    in.xyz = st.at.xyz;
+    in.support = D ? st.d_support : nullptr;
+    in.plain_offsets = st.d_offsets;
+    in.origin = reinterpret_cast<const float*>(d_tab);
+    in.own_cam = reinterpret_cast<const int*>(d_tab + org_b);
+    in.nbr_cam = reinterpret_cast<const int*>(d_tab + org_b + own_b);
+    in.nbr_mask = reinterpret_cast<const unsigned long long*>(d_tab + org_b + own_b + cam_b);
+    in.T = T;
+    in.n = n;
+    in.D = D;
+    in.M = (unsigned)v.M;
+    in.voxel = v.voxel_size;
+    in.inv = v.inv;
+    in.end_margin = cv->end_margin;
+    in.max_steps = cv->max_steps;
+    const long long E = ((long long)D + 1) * T;  // candidates, camera-major
+    const long long per = (1ll << 31) / BLOCK;   // workgroups of one dispatch (for_ref_slices)
+    const long long eblocks = (E + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < eblocks; b0 += per)
+        hipLaunchKernelGGL(k_vmap_carve, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, E,
+                           v.tb, v.crossings, v.ends, d_tot);
+    HIP_TRY(hipGetLastError());
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end, with the totals
+    cv->rays_total = (long long)h_tot[0];
+    cv->rays_skipped = (long long)h_tot[1];
+    cv->cells_visited = (long long)h_tot[2];
+    cv->cells_hit = (long long)h_tot[3];
+    cv->ends_hit = (long long)h_tot[4];
+    return SDM_OK;
+}
+
+int sdm_vmap_fetch_evidence(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_vmap_evidence* ev)
+{
+    if (!c || !ev) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (!ev->crossings && !ev->ends) return fail(SDM_EINVAL, "no output requested");
+    if (count < 0 || ev->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
+    if (count > ev->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
+    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
+        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
+    const bool dev = ev->on_device != 0;
+    if (dev && (((uintptr_t)ev->crossings | (uintptr_t)ev->ends) % 8 || (uintptr_t)ids % 4))
+        return fail(SDM_EINVAL, "device buffer not aligned (crossings, ends: 8 B; ids: 4 B)");
+    if (ids && !dev)
+        for (long long j = 0; j < count; j++)
+            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (count == 0) return SDM_OK;
+    const size_t m = (size_t)count;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const unsigned long long *src_cr = v.crossings, *src_en = v.ends;  // (null: no carve has run, every counter reads 0)
+    unsigned* h_bad = nullptr;
+    if (!ids) {
+        if (src_cr) src_cr += first, src_en += first;
+    } else {
+        // ids, the flag and -- for host destinations -- one dense region per requested counter
+        const size_t ids_b = ext_align(4 * m), b8 = ext_align(8 * m);
+        int rc;
+        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, ids_b + 256 + (dev ? 0 : 2 * b8))) ||
+            (rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256)))
+            return rc;
+        unsigned char* b = v.d_out;
+        const unsigned* d_ids = ids;
+        unsigned* d_bad = reinterpret_cast<unsigned*>(b + ids_b);
+        h_bad = reinterpret_cast<unsigned*>(v.h_pin);
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(b, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
+            d_ids = reinterpret_cast<const unsigned*>(b);
+        }
+        unsigned long long* dst_cr = dev ? ev->crossings : ev->crossings ? reinterpret_cast<unsigned long long*>(b + ids_b + 256) : nullptr;
+        unsigned long long* dst_en = dev ? ev->ends : ev->ends ? reinterpret_cast<unsigned long long*>(b + ids_b + 256 + b8) : nullptr;
+        HIP_TRY(hipMemsetAsync(d_bad, 0, 4, c->stream));
+        const long long per = (1ll << 31) / BLOCK;
+        const long long blocks = (count + BLOCK - 1) / BLOCK;
+        for (long long b0 = 0; b0 < blocks; b0 += per)
+            hipLaunchKernelGGL(k_vmap_evidence, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, src_cr, src_en,
+                               d_ids, count, b0 * BLOCK, (unsigned)v.M, dst_cr, dst_en, d_bad);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+        src_cr = dst_cr, src_en = dst_en;
+    }
+    if (!ids || !dev) {  // one copy per counter of exactly count elements (zeros before the first carve)
+        unsigned long long* dst[2] = {ev->crossings, ev->ends};
+        const unsigned long long* src[2] = {src_cr, src_en};
+        for (int k = 0; k < 2; k++) {
+            if (!dst[k]) continue;
+            if (src[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], 8 * m, kind, c->stream));
+            else if (dev) HIP_TRY(hipMemsetAsync(dst[k], 0, 8 * m, c->stream));
+            else std::memset(dst[k], 0, 8 * m);
+        }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
