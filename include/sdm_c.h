@@ -531,8 +531,8 @@ int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, in
  * the counts, the end.  sdm_vmap_fetch: one copy per field of exactly count elements (range form), after one gather
  * launch (ids form).
  * Limits: a keyframe's contribution cannot be removed; stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
- * integrate the resident slots again); free-space evidence is kept per entry by sdm_vmap_carve (below), camera lists on
- * the persistent map remain later work; one rank only. */
+ * integrate the resident slots again); free-space evidence is kept per entry by sdm_vmap_carve and the camera
+ * lists by sdm_vmap_observe (both below); one rank only. */
 typedef struct {
     long long voxels;       /* M */
     long long points;       /* mergeable points integrated */
@@ -627,6 +627,117 @@ int sdm_vmap_carve(sdm_ctx *ctx, int n, const int *slots, int n_nbr, const int *
                    int source, double max_sigma, double min_rho, sdm_vmap_carve_args *cv);
 int sdm_vmap_fetch_evidence(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
                             sdm_vmap_evidence *ev);
+/* Camera lists on the persistent map, kept as an append-only observation log: every entry accumulates, across calls, the
+ * set of keyframe TAGS that saw any point of its voxel, and every sdm_vmap_observe reports exactly which (entry, tag)
+ * pairs are new.  An online caller integrates a finished block, observes it, and fetches the created range of the log: a
+ * pair on an entry the same block created belongs to that entry's `new point: [x; y; z], KF_ind1, ..., KF_indN`, a pair on
+ * an older entry is an `observation: camIndex, pointIndex`.  Nothing in the reference does this; the semantics below are
+ * this library's (tests/vmap_obs_np.py restates them in NumPy).  Requires an open map; voxel_size, inv, the cell
+ * floorf(xyz_k * inv) and mergeability are sdm_vmap_integrate's.
+ *   - State: observations k = 0 .. E-1, each a pair (entry id, tag); no pair is stored twice.  E = 0 after sdm_vmap_open
+ *     and sdm_vmap_clear; sdm_vmap_close and sdm_destroy free everything.  Log indices never change.
+ *   - Plain cloud: sdm_vmap_observe reads the plain cloud g = 0 .. T-1 of (n, slots, source, max_sigma, min_rho) exactly as
+ *     sdm_vmap_integrate and sdm_vmap_carve do and, with n_nbr >= 1, the support words of sdm_extract_points_support for
+ *     the same arguments.  n_nbr == 0 with nbr_slots == NULL and nbr_tags == NULL is allowed, as in sdm_vmap_carve: the
+ *     point's own camera is then its only one and no support pass runs.
+ *   - Tags: the tag of slot slots[i] is tags[i], or the slot number when tags == NULL; the tag of column j of row i is
+ *     nbr_tags[i*n_nbr + j], or nbr_slots[i*n_nbr + j] when nbr_tags == NULL.  Every tag must lie in [0, 2^31).  Tags are
+ *     the persistent camera identity (slots are recycled in an online run): pass the keyframe ids, the same ones given
+ *     to sdm_vmap_integrate.
+ *   - Cameras of a point: C(g) = {tag(slots[i(g)])} U {tag of column j : bit j of support[g]}, i(g) the index of the
+ *     point's slot.  C(g) is a SET of tags: columns with equal tags collapse, and a column whose tag equals the point's
+ *     own tag falls out.
+ *   - Entry of a point: id(g) = the entry of the voxel of the point's staged xyz, if the point is mergeable and the map
+ *     holds that voxel; otherwise the point is UNMAPPED: it adds 1 to `unmapped` and contributes nothing.  The map is
+ *     read, not changed: no id, record, multiplicity, epoch, evidence counter or field of sdm_vmap_get_info moves.  The
+ *     recipe is: integrate a block, then observe it (then carve it, if evidence is wanted).
+ *   - Result: defined as if the mapped points were processed in increasing g, and within a point its tags in ascending
+ *     order: a pair (id(g), t) not yet stored is appended with index E, then E += 1.  `candidates` adds |C(g)| per mapped
+ *     point.
+ *   - Delta (sdm_vmap_observe_delta, all outs): plain_total = T, unmapped, candidates, first_created = E before the call,
+ *     created; the new observations are log entries first_created .. first_created + created - 1.
+ *   - Invariants: on a fixed map, observing slots s0 .. sk in one call, in k+1 calls of one slot, or in any split into
+ *     consecutive groups leaves a byte-identical log.  Observing the same slots again with unchanged planes creates
+ *     nothing.  After one sdm_vmap_integrate into an empty map and one sdm_vmap_observe of the same arguments with
+ *     tags == nbr_tags == NULL, the list of every entry equals the cam_slots list sdm_extract_points_voxel_cameras
+ *     returns for the kept point with the same (tag, pixel), and `unmapped` equals its unmergeable plain points.  On a
+ *     fixed map the per-entry lists, though not the log order, are independent of the order of the calls.
+ * Everything is integer: every returned array is bitwise the same from run to run.
+ * sdm_vmap_fetch_observations returns log entries first .. first + count - 1 into out->entry (u32) and / or out->tag (int):
+ * one plain copy per field of exactly count elements.  The pointers follow out->on_device, 4-byte aligned there.
+ * sdm_vmap_fetch_cameras returns, for entries first .. first + count - 1 (ids == NULL) or ids[0 .. count) (first must be
+ * 0; ids may repeat; ids follow cams->on_device, 4-byte aligned there), the tags of requested entry j in strictly
+ * ascending order: cam_tags[cam_offsets[j] .. cam_offsets[j + 1]), cam_offsets[0] = 0, cam_offsets[count] = cam_total.
+ * An entry never observed has an empty list.  The rules are sdm_voxel_cameras': at least one of the two pointers;
+ * cam_tags == NULL gives the offsets only and cam_capacity is ignored; cam_total > cam_capacity with cam_tags != NULL is
+ * SDM_EINVAL with cam_total filled and neither array written; cam_offsets holds capacity + 1 entries and is 8-byte,
+ * cam_tags 4-byte aligned on the device.  Reading changes nothing, so the caller sizes cam_tags and calls again.
+ * sdm_vmap_get_obs_info: observations = E, calls = successful sdm_vmap_observe calls since open / clear, table_slots and
+ * rehashes of the observation set (0 slots before the first observe with a plain point).
+ * Errors, all raised before any state changes (a refused call leaves the log, both infos and full fetches as they were):
+ *   SDM_ESTATE: no open map; the slot and neighbour states sdm_extract_points / sdm_extract_points_support refuse.
+ *   SDM_EINVAL: their argument errors; ob == NULL; a tag outside [0, 2^31); n_nbr < 0 or > max_neighbours; n_nbr == 0 with
+ *     a table; n_nbr >= 1 without nbr_slots; nbr_tags without nbr_slots; E + B > 2^30, B = sum_i T_i x L_i the a-priori
+ *     bound on new pairs (T_i the plain points of slot i, L_i the distinct tags of row i including its own): the set would
+ *     pass 2^31 slots; T x Lmax > 2^40, Lmax the largest L_i: the candidate index space the scans address; the fetch
+ *     errors exactly as sdm_vmap_fetch's (count < 0, count > capacity, a range beyond E or M, an id >= M, first != 0 with
+ *     ids, a misaligned device pointer, no destination); sdm_vmap_fetch_cameras also when min(count, 2048) x (distinct
+ *     tags observed since open / clear) >= 2^32: the list pass scans 32-bit sums.
+ *   SDM_EHIP: an allocation failure while growing -- everything is allocated before anything is inserted.
+ * On a refusal the outs of ob are 0, except plain_total once known.
+ * Changes no plane, flag, list or counter of the engine except sdm_stats::table_stagings as sdm_extract_points_support
+ * does, and uses scratch of its own: interleaved sdm_extract_points_voxel*, sdm_vmap_integrate and sdm_vmap_carve calls
+ * are undisturbed.
+ * Cost per sdm_vmap_observe: sdm_extract_points' passes (20 B per plain point staged) and, with neighbours,
+ * sdm_extract_points_support's pass: proportional to T.  Then one lane per candidate (g, d), d = 0 .. Lmax-1: per live
+ * candidate one read-only probe of the map's table and one probe of the observation set with two 64-bit atomics (a
+ * compare-and-swap and a min), 4 B of set position per candidate, two more passes over those 4 B: proportional to
+ * T x Lmax.  Per created pair 12 B of log, an exchange and an add on its entry.  Only in a growth is anything proportional
+ * to E: when 2 (E + B) exceeds the set's slots a set of the next sufficient power of two is made and every old slot
+ * re-inserted (`rehashes` counts these); the log grows geometrically by device copies.  Three host waits per call: T, the
+ * totals, the end.  sdm_vmap_fetch_cameras: one lane per requested entry walks and sorts its list (insertion, quadratic
+ * in the list's length); two host waits: the total, the end.
+ * Memory: 20 B per set slot (at least 2 (E + B) slots, so at least 40 B per pair of the bound), 12 B per log entry of
+ * capacity (at least E + B), 8 B per record of capacity, allocated at the first observe.
+ * Limits: set and log are sized a priori by B, which counts every candidate as new -- a block observed by many
+ * neighbours reserves far more than it creates -- and they never shrink before sdm_vmap_close (sdm_vmap_clear keeps the
+ * capacity); the lists go stale with sdm_set_pose exactly as the stored xyz do (remedy: sdm_vmap_clear, integrate and
+ * observe the resident slots again); an observation cannot be removed: removing one and shrinking the camera lists on
+ * the persistent map remain later work; one rank only. */
+typedef struct {
+    long long plain_total;     /* out: T */
+    long long unmapped;        /* out: plain points without an entry */
+    long long candidates;      /* out: sum of |C(g)| over the mapped points */
+    long long first_created;   /* out: E before the call */
+    long long created;         /* out */
+} sdm_vmap_observe_delta;
+typedef struct {
+    unsigned *entry;           /* [capacity] or NULL */
+    int *tag;                  /* [capacity] or NULL */
+    long long capacity;
+    int on_device;             /* pointers are device memory of this context's GPU, 4-byte aligned */
+} sdm_vmap_observations;
+typedef struct {
+    long long *cam_offsets;    /* [capacity + 1] or NULL */
+    int *cam_tags;             /* [cam_capacity] or NULL */
+    long long capacity;        /* in: entries cam_offsets serves; count must not exceed it */
+    long long cam_capacity;    /* in */
+    int on_device;             /* pointers (and ids) are device memory: cam_offsets 8-byte, cam_tags and ids 4-byte aligned */
+    long long cam_total;       /* out: sum of the requested lists' lengths */
+} sdm_vmap_cameras;
+typedef struct {
+    long long observations;    /* E */
+    long long calls;           /* successful sdm_vmap_observe calls since open / clear */
+    long long table_slots;     /* slots of the observation set */
+    long long rehashes;        /* its growths since open / clear */
+} sdm_vmap_obs_info;
+int sdm_vmap_observe(sdm_ctx *ctx, int n, const int *slots, const int *tags /*[n] or NULL*/, int n_nbr,
+                     const int *nbr_slots /*[n][n_nbr] or NULL*/, const int *nbr_tags /*[n][n_nbr] or NULL*/, int source,
+                     double max_sigma, double min_rho, sdm_vmap_observe_delta *ob);
+int sdm_vmap_get_obs_info(sdm_ctx *ctx, sdm_vmap_obs_info *info);
+int sdm_vmap_fetch_observations(sdm_ctx *ctx, long long first, long long count, sdm_vmap_observations *out);
+int sdm_vmap_fetch_cameras(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
+                           sdm_vmap_cameras *cams);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

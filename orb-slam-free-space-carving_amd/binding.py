@@ -89,6 +89,29 @@ class VmapEvidence(C.Structure):
     _fields_ = [("crossings", C.c_void_p), ("ends", C.c_void_p), ("capacity", C.c_longlong), ("on_device", C.c_int)]
 
 
+class VmapObserveDelta(C.Structure):
+    """sdm_vmap_observe_delta"""
+    _fields_ = [("plain_total", C.c_longlong), ("unmapped", C.c_longlong), ("candidates", C.c_longlong),
+                ("first_created", C.c_longlong), ("created", C.c_longlong)]
+
+
+class VmapObservations(C.Structure):
+    """sdm_vmap_observations"""
+    _fields_ = [("entry", C.c_void_p), ("tag", C.c_void_p), ("capacity", C.c_longlong), ("on_device", C.c_int)]
+
+
+class VmapCameras(C.Structure):
+    """sdm_vmap_cameras"""
+    _fields_ = [("cam_offsets", C.c_void_p), ("cam_tags", C.c_void_p), ("capacity", C.c_longlong),
+                ("cam_capacity", C.c_longlong), ("on_device", C.c_int), ("cam_total", C.c_longlong)]
+
+
+class VmapObsInfo(C.Structure):
+    """sdm_vmap_obs_info"""
+    _fields_ = [("observations", C.c_longlong), ("calls", C.c_longlong), ("table_slots", C.c_longlong),
+                ("rehashes", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -106,6 +129,9 @@ VMAP_FIELDS = tuple(POINT_FIELDS) + tuple(VMAP_EXTRA_FIELDS)
 # sdm_vmap_fetch_evidence fields, and the outs of sdm_vmap_carve
 VMAP_EVIDENCE_FIELDS = ("crossings", "ends")
 VMAP_CARVE_OUTS = ("plain_total", "rays_total", "rays_skipped", "cells_visited", "cells_hit", "ends_hit")
+# sdm_vmap_fetch_observations fields, and the outs of sdm_vmap_observe
+VMAP_OBSERVATION_FIELDS = {"entry": np.uint32, "tag": np.int32}
+VMAP_OBSERVE_OUTS = ("plain_total", "unmapped", "candidates", "first_created", "created")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -173,6 +199,11 @@ SYMBOLS = [
     ("sdm_vmap_carve", C.c_int, [_ctx, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_double, C.c_double,
                                  C.POINTER(VmapCarveArgs)]),
     ("sdm_vmap_fetch_evidence", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(VmapEvidence)]),
+    ("sdm_vmap_observe", C.c_int, [_ctx, C.c_int, _ip, _ip, C.c_int, _ip, _ip, C.c_int, C.c_double, C.c_double,
+                                   C.POINTER(VmapObserveDelta)]),
+    ("sdm_vmap_get_obs_info", C.c_int, [_ctx, C.POINTER(VmapObsInfo)]),
+    ("sdm_vmap_fetch_observations", C.c_int, [_ctx, C.c_longlong, C.c_longlong, C.POINTER(VmapObservations)]),
+    ("sdm_vmap_fetch_cameras", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(VmapCameras)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1030,6 +1061,135 @@ class Engine:
         ev.on_device = 1 if kinds == {"device"} else 0
         self._check(self.lib.sdm_vmap_fetch_evidence(self.ctx, idp, int(first), int(count), C.byref(ev)))
         return {f: a[:count] for f, a in out.items()}
+
+    def vmap_observe(self, slots, nbrs=None, tags=None, nbr_tags=None, source=1, max_sigma=0.01, min_rho=1e-6):
+        """Camera lists on the voxel map (sdm_vmap_observe): every entry that holds the voxel of a plain point of `slots`
+        learns the tags of the cameras that saw the point -- the observing slot's and, with nbrs int32[n, n_nbr], those
+        of the neighbours that confirm it as extract_points_support reports them.  tags[i] names slots[i] and
+        nbr_tags[i, j] names nbrs[i, j] (defaults: the slot numbers); pass the keyframe ids given to vmap_integrate.
+        New (entry, tag) pairs are appended to the observation log.  The map itself is only read: integrate a block,
+        then observe it.  Returns {"plain_total", "unmapped", "candidates", "first_created", "created"}: the new pairs
+        are log entries first_created .. first_created + created - 1.  A refusal raises SdmError with .plain_total."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        n = len(sl)
+        n_nbr, nbp, tp, ntp = 0, None, None, None
+        if nbrs is not None:
+            nb = np.ascontiguousarray(np.asarray(nbrs, dtype=np.int32))
+            if nb.ndim != 2 or nb.shape[0] != n:
+                raise ValueError("nbrs: need int32[n, n_nbr], one row per slot")
+            n_nbr, nbp = nb.shape[1], nb.ctypes.data_as(_ip)
+        if tags is not None:
+            tg = np.ascontiguousarray(np.asarray(tags, dtype=np.int32).reshape(-1))
+            if len(tg) != n:
+                raise ValueError("tags: need one per slot")
+            tp = tg.ctypes.data_as(_ip)
+        if nbr_tags is not None:
+            nt = np.ascontiguousarray(np.asarray(nbr_tags, dtype=np.int32))
+            if nbrs is not None and nt.shape != nb.shape:
+                raise ValueError("nbr_tags: need the shape of nbrs")
+            ntp = nt.ctypes.data_as(_ip)
+        ob = VmapObserveDelta()
+        rc = self.lib.sdm_vmap_observe(self.ctx, n, sl.ctypes.data_as(_ip), tp, n_nbr, nbp, ntp, int(source),
+                                       float(max_sigma), float(min_rho), C.byref(ob))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.plain_total = int(ob.plain_total)
+            raise e
+        return {f: int(getattr(ob, f)) for f in VMAP_OBSERVE_OUTS}
+
+    def vmap_obs_info(self):
+        """{"observations", "calls", "table_slots", "rehashes"} of the observation log (sdm_vmap_get_obs_info)"""
+        info = VmapObsInfo()
+        self._check(self.lib.sdm_vmap_get_obs_info(self.ctx, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in VmapObsInfo._fields_}
+
+    def vmap_fetch_observations(self, first=0, count=None, fields=tuple(VMAP_OBSERVATION_FIELDS), out=None):
+        """Entries first .. first + count - 1 of the observation log (count None: to the end): entry uint32[m] and tag
+        int32[m] (sdm_vmap_fetch_observations).  out: {field: preallocated array (pageable, or pinned from host_alloc)
+        or torch device tensor of 4-byte elements}.  Returns {field: array}."""
+        if count is None:
+            count = max(self.vmap_obs_info()["observations"] - int(first), 0)
+        if out is None:
+            for f in fields:
+                if f not in VMAP_OBSERVATION_FIELDS:
+                    raise ValueError("unknown observation field %r" % (f,))
+            out = {f: np.empty(max(int(count), 1), VMAP_OBSERVATION_FIELDS[f]) for f in fields}
+        vo = VmapObservations()
+        kinds = set()
+        cap = None
+        for f, a in out.items():
+            if f not in VMAP_OBSERVATION_FIELDS:
+                raise ValueError("unknown observation field %r" % (f,))
+            ptr, m = self._dest(f, a, VMAP_OBSERVATION_FIELDS[f], 1, kinds)
+            setattr(vo, f, ptr)
+            cap = m if cap is None else min(cap, m)
+        if len(kinds) > 1:
+            raise ValueError("out mixes host arrays and device tensors")
+        vo.capacity = cap if cap is not None else 0
+        vo.on_device = 1 if kinds == {"device"} else 0
+        self._check(self.lib.sdm_vmap_fetch_observations(self.ctx, int(first), int(count), C.byref(vo)))
+        return {f: a[:count] for f, a in out.items()}
+
+    def vmap_fetch_cameras(self, ids=None, first=0, count=None, out=None):
+        """The camera lists of the voxel map's entries (sdm_vmap_fetch_cameras), selected as vmap_fetch selects (ids may
+        repeat): {"cam_offsets": int64[count + 1], "cam_tags": int32[cam_total]} -- the tags of requested entry j, in
+        ascending order, are cam_tags[cam_offsets[j]:cam_offsets[j + 1]]; an entry never observed has an empty list.
+        Without `out` the lists are sized by a first call that takes the offsets only.  out: {"cam_offsets": int64 array
+        or 8-byte device tensor of count + 1 elements, "cam_tags": int32 array or 4-byte device tensor}, either or both;
+        a cam_tags too small raises SdmError with .cam_total."""
+        kinds = set()
+        idp = None
+        if ids is not None:
+            if isinstance(ids, np.ndarray) or not getattr(ids, "is_cuda", False):
+                ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+            idp, nid = self._dest("ids", ids, np.uint32, 1, kinds)
+            if count is None:
+                count = nid
+            elif count > nid:
+                raise ValueError("ids: fewer than count")
+        elif count is None:
+            count = max(self.vmap_info()["voxels"] - int(first), 0)
+        count = int(count)
+        vc = VmapCameras()
+
+        def call():
+            rc = self.lib.sdm_vmap_fetch_cameras(self.ctx, idp, int(first), count, C.byref(vc))
+            if rc:
+                e = SdmError(rc, self.lib.sdm_last_error().decode())
+                e.cam_total = int(vc.cam_total)
+                raise e
+
+        if out is None:
+            if kinds == {"device"}:
+                raise ValueError("device ids need device destinations in out")
+            offs = np.empty(count + 1, np.int64)
+            vc.cam_offsets, vc.capacity = offs.ctypes.data, count
+            call()  # the offsets alone size the tags
+            total = int(vc.cam_total)
+            tags = np.empty(max(total, 1), np.int32)
+            vc.cam_tags, vc.cam_capacity = tags.ctypes.data, total
+            call()
+            return {"cam_offsets": offs, "cam_tags": tags[:total]}
+        for f in out:
+            if f not in ("cam_offsets", "cam_tags"):
+                raise ValueError("unknown camera field %r" % (f,))
+        vc.capacity = count
+        if out.get("cam_offsets") is not None:
+            vc.cam_offsets, m = self._dest("cam_offsets", out["cam_offsets"], np.int64, 1, kinds)
+            vc.capacity = m - 1
+        if out.get("cam_tags") is not None:
+            vc.cam_tags, vc.cam_capacity = self._dest("cam_tags", out["cam_tags"], np.int32, 1, kinds)
+        if len(kinds) > 1:
+            raise ValueError("ids and out mix host arrays and device tensors")
+        vc.on_device = 1 if kinds == {"device"} else 0
+        call()
+        total = int(vc.cam_total)
+        res = {"cam_total": total}
+        if out.get("cam_offsets") is not None:
+            res["cam_offsets"] = out["cam_offsets"][:count + 1]
+        if out.get("cam_tags") is not None:
+            res["cam_tags"] = out["cam_tags"][:total]
+        return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

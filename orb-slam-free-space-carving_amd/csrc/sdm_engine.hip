@@ -36,6 +36,7 @@
 #include "sdm_carve.h"
 #include "sdm_vmap.h"
 #include "sdm_vmap_carve.h"
+#include "sdm_vmap_obs.h"
 
 using namespace sdm;
 
@@ -284,6 +285,27 @@ struct sdm_ctx {
         size_t out_bytes = 0;
         unsigned char* h_pin = nullptr;
         size_t pin_bytes = 0;
+        // the observation log (sdm_vmap_observe, sdm_vmap_obs.h): nothing is allocated before the first observe with a
+        // plain point.  The set, the log, the per-entry heads and lengths (for rec_cap entries, grown with the records) and
+        // a scratch, a staging and a pinned mirror of their own, so that no other call's scratch is touched
+        struct Obs {
+            long long E = 0, calls = 0, rehashes = 0;
+            unsigned long long cap = 0;  // set slots
+            unsigned char* d_table = nullptr;
+            VobsTable tb{};
+            long long log_cap = 0;
+            unsigned char* d_log = nullptr;
+            VobsLog log{};
+            unsigned char* d_ent = nullptr;  // last_obs[rec_cap] | ncam[rec_cap]
+            unsigned *last_obs = nullptr, *ncam = nullptr;
+            std::vector<int> seen;  // the distinct tags observed since open / clear, ascending: no list is longer
+            unsigned char* d_scratch = nullptr;
+            size_t scratch_bytes = 0;
+            unsigned char* d_out = nullptr;
+            size_t out_bytes = 0;
+            unsigned char* h_pin = nullptr;
+            size_t pin_bytes = 0;
+        } obs;
     } vmap;
 
     // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
@@ -1148,6 +1170,12 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->vmap.d_scratch);
     (void)hipFree(c->vmap.d_out);
     (void)hipHostFree(c->vmap.h_pin);
+    (void)hipFree(c->vmap.obs.d_table);
+    (void)hipFree(c->vmap.obs.d_log);
+    (void)hipFree(c->vmap.obs.d_ent);
+    (void)hipFree(c->vmap.obs.d_scratch);
+    (void)hipFree(c->vmap.obs.d_out);
+    (void)hipHostFree(c->vmap.obs.h_pin);
     (void)hipHostFree(c->h_vcam);
     (void)hipHostFree(c->h_ext);
     (void)hipFree(c->obs.ids);
@@ -2840,6 +2868,23 @@ static int vmap_make_evidence(sdm_ctx* c, long long cap, unsigned char** block, 
     return SDM_OK;
 }
 
+// one block for the observations' per-entry arrays of `cap` entries: last_obs (no observation) | ncam (0)
+static int vmap_make_obs_entries(sdm_ctx* c, long long cap, unsigned char** block, unsigned** last_obs, unsigned** ncam)
+{
+    const size_t b4 = ext_align(4 * (size_t)std::max(cap, 1ll));
+    HIP_TRY(hipMalloc((void**)block, 2 * b4));
+    *last_obs = reinterpret_cast<unsigned*>(*block);
+    *ncam = reinterpret_cast<unsigned*>(*block + b4);
+    hipError_t e = hipMemsetAsync(*block, 0xff, b4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(*block + b4, 0, b4, c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(*block);
+        *block = nullptr;
+        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    return SDM_OK;
+}
+
 static void vmap_free(sdm_ctx* c)
 {
     sdm_ctx::Vmap& v = c->vmap;
@@ -2849,6 +2894,12 @@ static void vmap_free(sdm_ctx* c)
     (void)hipFree(v.d_scratch);
     (void)hipFree(v.d_out);
     (void)hipHostFree(v.h_pin);
+    (void)hipFree(v.obs.d_table);
+    (void)hipFree(v.obs.d_log);
+    (void)hipFree(v.obs.d_ent);
+    (void)hipFree(v.obs.d_scratch);
+    (void)hipFree(v.obs.d_out);
+    (void)hipHostFree(v.obs.h_pin);
     v = sdm_ctx::Vmap{};
 }
 
@@ -2892,8 +2943,16 @@ int sdm_vmap_clear(sdm_ctx* c)
     HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
     HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
     if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, 2 * ext_align(8 * (size_t)v.rec_cap), c->stream));
+    if (v.obs.d_table) HIP_TRY(hipMemsetAsync(v.obs.d_table, 0xff, 20 * (size_t)v.obs.cap, c->stream));
+    if (v.obs.d_ent) {  // (the log keeps its capacity; its content is dead with E = 0)
+        const size_t b4 = ext_align(4 * (size_t)v.rec_cap);
+        HIP_TRY(hipMemsetAsync(v.obs.d_ent, 0xff, b4, c->stream));
+        HIP_TRY(hipMemsetAsync(v.obs.d_ent + b4, 0, b4, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     v.M = v.points = v.dropped = v.calls = v.rehashes = 0;
+    v.obs.E = v.obs.calls = v.obs.rehashes = 0;
+    v.obs.seen.clear();
     return SDM_OK;
 }
 
@@ -2965,9 +3024,21 @@ static int vmap_grow(sdm_ctx* c, long long need)
             (void)hipFree(block);
             return rc;
         }
+        unsigned char* ent = nullptr;  // so do the observations' heads and lengths: M entries copied, the rest empty
+        unsigned *nlast = nullptr, *nncam = nullptr;
+        if (v.obs.d_ent && (rc = vmap_make_obs_entries(c, cap, &ent, &nlast, &nncam))) {
+            (void)hipFree(block);
+            (void)hipFree(evid);
+            return rc;
+        }
         const size_t m = (size_t)v.M;
         hipError_t e = hipSuccess;
-        if (evid) {
+        if (ent) {
+            if (m) e = hipMemcpyAsync(nlast, v.obs.last_obs, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (m && e == hipSuccess) e = hipMemcpyAsync(nncam, v.obs.ncam, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
+        }
+        if (evid && e == hipSuccess) {
             if (m) e = hipMemcpyAsync(ncr, v.crossings, 8 * m, hipMemcpyDeviceToDevice, c->stream);
             if (m && e == hipSuccess) e = hipMemcpyAsync(nen, v.ends, 8 * m, hipMemcpyDeviceToDevice, c->stream);
             if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
@@ -2985,7 +3056,14 @@ static int vmap_grow(sdm_ctx* c, long long need)
         if (e != hipSuccess) {
             (void)hipFree(block);
             (void)hipFree(evid);
+            (void)hipFree(ent);
             return fail(SDM_EHIP, std::string("voxel map records: ") + hipGetErrorString(e));
+        }
+        if (ent) {  // (waited for above, as the records are)
+            (void)hipFree(v.obs.d_ent);
+            v.obs.d_ent = ent;
+            v.obs.last_obs = nlast;
+            v.obs.ncam = nncam;
         }
         if (evid) {  // (waited for above, as the records are)
             (void)hipFree(v.d_evid);
@@ -3386,6 +3464,374 @@ int sdm_vmap_fetch_evidence(sdm_ctx* c, const unsigned* ids, long long first, lo
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
+    return SDM_OK;
+}
+
+// ---- camera lists on the persistent voxel map: the observation log (sdm_vmap_obs.h) --------------------------------------
+// one block for the set: keys | ord | idx (20 B per slot), all ones: empty keys, ord's identity, no index
+static int vobs_make_table(sdm_ctx* c, unsigned long long cap, unsigned char** block, VobsTable* tb)
+{
+    const size_t n = (size_t)cap;
+    HIP_TRY(hipMalloc((void**)block, 20 * n));
+    unsigned char* p = *block;
+    tb->keys = reinterpret_cast<unsigned long long*>(p);
+    tb->ord = reinterpret_cast<unsigned long long*>(p + 8 * n);
+    tb->idx = reinterpret_cast<unsigned*>(p + 16 * n);
+    tb->mask = cap - 1;
+    const hipError_t e = hipMemsetAsync(p, 0xff, 20 * n, c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(*block);
+        *block = nullptr;
+        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    return SDM_OK;
+}
+
+// set, log and per-entry arrays for `need` observations, made before anything is inserted; the old ones stay intact if
+// an allocation fails
+static int vobs_grow(sdm_ctx* c, long long need)
+{
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    int rc;
+    if (!o.d_ent && (rc = vmap_make_obs_entries(c, v.rec_cap, &o.d_ent, &o.last_obs, &o.ncam))) return rc;
+    if (!o.d_table || 2ull * (unsigned long long)need > o.cap) {
+        unsigned long long cap = std::max(o.cap, 1024ull);
+        while (cap < 2ull * (unsigned long long)need) cap <<= 1;
+        unsigned char* block = nullptr;
+        VobsTable nw{};
+        if ((rc = vobs_make_table(c, cap, &block, &nw))) return rc;
+        if (o.d_table) {
+            unsigned* d_flag = reinterpret_cast<unsigned*>(o.d_scratch);  // (the caller has sized the scratch)
+            unsigned* h_flag = reinterpret_cast<unsigned*>(o.h_pin);
+            hipError_t e = hipMemsetAsync(d_flag, 0, 4, c->stream);
+            const unsigned long long per = 1ull << 31;  // work-items of one dispatch
+            for (unsigned long long h0 = 0; h0 < o.cap && e == hipSuccess; h0 += per)
+                hipLaunchKernelGGL(k_vobs_rehash, dim3((unsigned)((std::min(per, o.cap - h0) + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                                   c->stream, o.tb.keys, o.tb.idx, o.cap, h0, nw, d_flag);
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess || *h_flag) {
+                (void)hipFree(block);
+                return fail(SDM_EHIP, e != hipSuccess ? std::string("observation set rehash: ") + hipGetErrorString(e)
+                                                      : std::string("observation set overflow while rehashing"));
+            }
+            (void)hipFree(o.d_table);  // (only after the wait)
+            o.rehashes++;
+        }
+        o.d_table = block;
+        o.tb = nw;
+        o.cap = cap;
+    }
+    if (need > o.log_cap) {
+        const long long cap = std::max(need, 2 * o.log_cap);  // geometric: the copies amortise
+        const size_t b4 = ext_align(4 * (size_t)cap);
+        unsigned char* block = nullptr;
+        HIP_TRY(hipMalloc((void**)&block, 3 * b4));
+        VobsLog nl;
+        nl.entry = reinterpret_cast<unsigned*>(block);
+        nl.tag = reinterpret_cast<int*>(block + b4);
+        nl.prev = reinterpret_cast<unsigned*>(block + 2 * b4);
+        const size_t m = (size_t)o.E;
+        hipError_t e = hipSuccess;
+        if (m) {
+            e = hipMemcpyAsync(nl.entry, o.log.entry, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nl.tag, o.log.tag, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(nl.prev, o.log.prev, 4 * m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+        if (e != hipSuccess) {
+            (void)hipFree(block);
+            return fail(SDM_EHIP, std::string("observation log: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(o.d_log);
+        o.d_log = block;
+        o.log = nl;
+        o.log_cap = cap;
+    }
+    return SDM_OK;
+}
+
+int sdm_vmap_observe(sdm_ctx* c, int n, const int* slots, const int* tags, int n_nbr, const int* nbr_slots, const int* nbr_tags,
+                     int source, double max_sigma, double min_rho, sdm_vmap_observe_delta* ob)
+{
+    if (ob) ob->plain_total = ob->unmapped = ob->candidates = ob->first_created = ob->created = 0;
+    if (!c || !ob) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (n < 0 || (n > 0 && !slots)) return fail(SDM_EINVAL, "null or negative slot list");
+    if (n_nbr < 0) return fail(SDM_EINVAL, "negative n_nbr");
+    if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
+    if ((n_nbr == 0) != (nbr_slots == nullptr))
+        return fail(SDM_EINVAL, n_nbr ? "null nbr_slots" : "n_nbr == 0 with a neighbour table");
+    if (nbr_tags && !nbr_slots) return fail(SDM_EINVAL, "nbr_tags without nbr_slots");
+    const size_t nn = (size_t)n * (size_t)n_nbr;
+    if (tags)
+        for (int i = 0; i < n; i++)
+            if (tags[i] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
+    if (nbr_tags)
+        for (size_t i = 0; i < nn; i++)
+            if (nbr_tags[i] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
+
+    // the plain cloud (xyz and rho_sigma) and, with neighbours, the support words into the engine's staging
+    ExtractStaged st{};
+    st.support = n_nbr > 0;
+    sdm_point_buffers none{};
+    std::vector<long long> plain((size_t)n + 1, 0);
+    int rc = extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
+    if (rc) return rc;
+    const long long T = st.total;
+    ob->plain_total = T;
+
+    // per row the ascending list of its distinct tags with the columns that name each; the own tag's position is always
+    // live (extract_core has checked every slot's range, so a slot number is a valid tag; n_nbr <= 64)
+    std::vector<std::vector<std::pair<int, unsigned long long>>> lists((size_t)n);
+    std::vector<int> own((size_t)n, 0);
+    int Lmax = 1;
+    long long B = 0;
+    for (int i = 0; i < n; i++) {
+        auto& l = lists[(size_t)i];
+        const int mine = tags ? tags[i] : slots[i];
+        l.emplace_back(mine, 0ull);
+        for (int j = 0; j < n_nbr; j++) {
+            const size_t at = (size_t)i * (size_t)n_nbr + (size_t)j;
+            const int t = nbr_tags ? nbr_tags[at] : nbr_slots[at];
+            size_t k = 0;
+            while (k < l.size() && l[k].first != t) k++;
+            if (k == l.size()) l.emplace_back(t, 0ull);
+            l[k].second |= 1ull << j;
+        }
+        std::sort(l.begin(), l.end());  // (the tags are distinct: the masks never decide)
+        for (size_t k = 0; k < l.size(); k++)
+            if (l[k].first == mine) own[(size_t)i] = (int)k;
+        Lmax = std::max(Lmax, (int)l.size());
+        B += (plain[(size_t)i + 1] - plain[(size_t)i]) * (long long)l.size();
+    }
+    if (o.E + B > (1ll << 30))
+        return fail(SDM_EINVAL, "more than 2^30 observations and candidates: the observation set would exceed 2^31 slots");
+    const long long Ec = T * (long long)Lmax;  // candidates, point-major
+    if (Ec > (1ll << 40)) return fail(SDM_EINVAL, "more than 2^40 candidates (plain points x the longest row) in one call");
+    if (T == 0) {  // (extract_core has waited for the stream)
+        ob->first_created = o.E;
+        o.calls++;
+        return SDM_OK;
+    }
+
+    // scratch, pinned mirror and growth: everything is allocated before anything is inserted
+    const long long vt = (Ec + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t nl = (size_t)n * (size_t)Lmax;
+    const size_t where_b = ext_align(4 * (size_t)Ec), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1)),
+                 blk_b = ext_align(8 * (size_t)vb);
+    const size_t tag_b = ext_align(4 * nl), mask_b = ext_align(8 * nl), own_b = ext_align(4 * (size_t)n), tab_b = mask_b + tag_b + own_b;
+    if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, 512 + where_b + tcnt_b + toff_b + 2 * blk_b + tab_b))) return rc;
+    if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256 + tab_b))) return rc;
+    if ((rc = vobs_grow(c, o.E + B))) return rc;
+    unsigned char* p = o.d_scratch;
+    unsigned long long* d_ctr = reinterpret_cast<unsigned long long*>(p + 64);   // {unmapped, candidates, overflow}
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, unmapped, candidates, overflow}
+    p += 512;
+    unsigned* d_where = reinterpret_cast<unsigned*>(p);
+    p += where_b;
+    unsigned* d_cnt = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned char* d_tab = p;
+    unsigned char* h_tab = o.h_pin + 256;
+    unsigned long long* h_mask = reinterpret_cast<unsigned long long*>(h_tab);
+    int* h_tag = reinterpret_cast<int*>(h_tab + mask_b);
+    int* h_own = reinterpret_cast<int*>(h_tab + mask_b + tag_b);
+    for (int i = 0; i < n; i++) {
+        const auto& l = lists[(size_t)i];
+        h_own[i] = own[(size_t)i];
+        for (int d = 0; d < Lmax; d++) {
+            const bool have = (size_t)d < l.size();
+            h_tag[(size_t)i * (size_t)Lmax + (size_t)d] = have ? l[(size_t)d].first : 0;
+            h_mask[(size_t)i * (size_t)Lmax + (size_t)d] = have ? l[(size_t)d].second : 0ull;
+        }
+    }
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, 24, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_b, hipMemcpyHostToDevice, c->stream));
+    VobsIn in;
+    in.xyz = st.at.xyz;
+    in.support = n_nbr > 0 ? st.d_support : nullptr;
+    in.plain_offsets = st.d_offsets;
+    in.row_mask = reinterpret_cast<const unsigned long long*>(d_tab);
+    in.row_tag = reinterpret_cast<const int*>(d_tab + mask_b);
+    in.own = reinterpret_cast<const int*>(d_tab + mask_b + tag_b);
+    in.T = T;
+    in.n = n;
+    in.Lmax = Lmax;
+    in.inv = v.inv;
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long eblocks = (Ec + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < eblocks; b0 += per)
+        hipLaunchKernelGGL(k_vobs_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, Ec,
+                           v.tb, o.tb, d_where, d_ctr);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_where, Ec, t0,
+                           d_cnt);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt, vt, d_off, d_bsum);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)vb, d_boff);
+    hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off, d_boff, d_ctr, d_tot);
+    HIP_TRY(hipGetLastError());
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(o.h_pin);
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: created
+    if (h_tot[3]) return fail(SDM_EHIP, "observation set overflow");
+    const long long created = (long long)h_tot[0];
+    if (created > B) return fail(SDM_EHIP, "observation log: more pairs created than the a-priori bound");
+
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log, o.last_obs,
+                           o.ncam, d_where, (unsigned)o.E, Ec, t0, d_off, d_boff);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (const auto& l : lists)  // the tags seen so far bound every list's length (sdm_vmap_fetch_cameras' scan)
+        for (const auto& tm : l) {
+            const auto it = std::lower_bound(o.seen.begin(), o.seen.end(), tm.first);
+            if (it == o.seen.end() || *it != tm.first) o.seen.insert(it, tm.first);
+        }
+    ob->unmapped = (long long)h_tot[1];
+    ob->candidates = (long long)h_tot[2];
+    ob->first_created = o.E;
+    ob->created = created;
+    o.E += created;
+    o.calls++;
+    return SDM_OK;
+}
+
+int sdm_vmap_get_obs_info(sdm_ctx* c, sdm_vmap_obs_info* info)
+{
+    if (!c || !info) return fail(SDM_EINVAL, "null argument");
+    const sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    std::memset(info, 0, sizeof(*info));
+    info->observations = v.obs.E;
+    info->calls = v.obs.calls;
+    info->table_slots = (long long)v.obs.cap;
+    info->rehashes = v.obs.rehashes;
+    return SDM_OK;
+}
+
+int sdm_vmap_fetch_observations(sdm_ctx* c, long long first, long long count, sdm_vmap_observations* out)
+{
+    if (!c || !out) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (!out->entry && !out->tag) return fail(SDM_EINVAL, "no output requested");
+    if (count < 0 || out->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
+    if (count > out->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
+    if (first < 0 || first > v.obs.E || count > v.obs.E - first) return fail(SDM_EINVAL, "range beyond the log's observations");
+    const bool dev = out->on_device != 0;
+    if (dev && ((uintptr_t)out->entry | (uintptr_t)out->tag) % 4) return fail(SDM_EINVAL, "device buffer not aligned (entry, tag: 4 B)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (count == 0) return SDM_OK;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out->entry) HIP_TRY(hipMemcpyAsync(out->entry, v.obs.log.entry + first, 4 * (size_t)count, kind, c->stream));
+    if (out->tag) HIP_TRY(hipMemcpyAsync(out->tag, v.obs.log.tag + first, 4 * (size_t)count, kind, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDM_OK;
+}
+
+int sdm_vmap_fetch_cameras(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_vmap_cameras* cams)
+{
+    if (cams) cams->cam_total = 0;
+    if (!c || !cams) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (!cams->cam_offsets && !cams->cam_tags) return fail(SDM_EINVAL, "no camera output requested");
+    if (count < 0 || cams->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
+    if (cams->cam_tags && cams->cam_capacity < 0) return fail(SDM_EINVAL, "negative cam_capacity");
+    if (count > cams->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
+    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
+        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
+    const bool dev = cams->on_device != 0;
+    if (dev && ((uintptr_t)cams->cam_offsets % 8 || ((uintptr_t)cams->cam_tags | (uintptr_t)ids) % 4))
+        return fail(SDM_EINVAL, "device buffer not aligned (cam_offsets: 8 B; cam_tags, ids: 4 B)");
+    if (ids && !dev)
+        for (long long j = 0; j < count; j++)
+            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
+    if ((unsigned long long)std::min(count, (long long)EXT_SCAN) * (unsigned long long)o.seen.size() >= (1ull << 32))
+        return fail(SDM_EINVAL, "min(count, 2048) x (distinct tags observed) >= 2^32: the list pass scans 32-bit sums");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+
+    // ids, lengths, the scan's arrays and -- for host destinations -- the offsets; the tags' staging follows the total
+    const size_t m = (size_t)count;
+    const long long nb = (count + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t ids_b = ext_align(4 * m), len_b = ext_align(4 * m), toff_b = ext_align(4 * (m + 1)), blk_b = ext_align(8 * (size_t)nb),
+                 offs_b = ext_align(8 * (m + 1));
+    const size_t fixed_b = 256 + ids_b + len_b + toff_b + 2 * blk_b + offs_b;
+    int rc;
+    if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, fixed_b)) || (rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
+    unsigned char* p = o.d_scratch;
+    unsigned* d_bad = reinterpret_cast<unsigned*>(p);
+    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(p + 8);
+    p += 256;
+    unsigned* d_ids_own = reinterpret_cast<unsigned*>(p);
+    p += ids_b;
+    unsigned* d_len = reinterpret_cast<unsigned*>(p);
+    p += len_b;
+    unsigned* d_toff = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    long long* d_offs = dev ? cams->cam_offsets : cams->cam_offsets ? reinterpret_cast<long long*>(p) : nullptr;
+    const unsigned* d_ids = ids;
+    if (ids && !dev && count) {
+        HIP_TRY(hipMemcpyAsync(d_ids_own, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
+        d_ids = d_ids_own;
+    }
+    HIP_TRY(hipMemsetAsync(o.d_scratch, 0, 16, c->stream));
+    const long long per = (1ll << 31) / BLOCK;
+    const long long blocks = (count + BLOCK - 1) / BLOCK, oblocks = (count + 1 + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < blocks; b0 += per)
+        hipLaunchKernelGGL(k_vobs_list_count, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, o.ncam, d_ids, first,
+                           count, b0 * BLOCK, (unsigned)v.M, d_len, d_bad);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, d_len, count, d_toff, d_bsum);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)nb, d_boff);
+    // (the offsets go to a caller's device array only once the total is known to fit: the scan's arrays serve until then)
+    hipLaunchKernelGGL(k_vobs_list_offsets, dim3(1), dim3(BLOCK), 0, c->stream, d_toff, d_boff, count, count, (long long*)nullptr,
+                       d_total);
+    HIP_TRY(hipGetLastError());
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(o.h_pin);
+    HIP_TRY(hipMemcpyAsync(h_tot, o.d_scratch, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: the lists' total
+    if ((unsigned)h_tot[0]) return fail(SDM_EINVAL, "id beyond the map's entries");
+    const long long total = (long long)h_tot[1];
+    cams->cam_total = total;
+    if (cams->cam_tags && total > cams->cam_capacity)
+        return fail(SDM_EINVAL, "cam_capacity " + std::to_string(cams->cam_capacity) + " < " + std::to_string(total) +
+                                    " list entries (cam_total filled)");
+    int* d_tags = cams->cam_tags;
+    if (cams->cam_tags && !dev && total) {
+        if ((rc = ext_grow_dev(&o.d_out, &o.out_bytes, 4 * (size_t)total))) return rc;
+        d_tags = reinterpret_cast<int*>(o.d_out);
+    }
+    if (d_offs)
+        for (long long b0 = 0; b0 < oblocks; b0 += per)
+            hipLaunchKernelGGL(k_vobs_list_offsets, dim3((unsigned)std::min(per, oblocks - b0)), dim3(BLOCK), 0, c->stream, d_toff,
+                               d_boff, count, b0 * BLOCK, d_offs, d_total);
+    if (cams->cam_tags && total)
+        for (long long b0 = 0; b0 < blocks; b0 += per)
+            hipLaunchKernelGGL(k_vobs_list_fill, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, o.log, o.last_obs,
+                               d_ids, first, count, b0 * BLOCK, (unsigned)v.M, d_len, d_toff, d_boff, d_tags);
+    HIP_TRY(hipGetLastError());
+    if (!dev) {
+        if (cams->cam_offsets) HIP_TRY(hipMemcpyAsync(cams->cam_offsets, d_offs, 8 * (m + 1), hipMemcpyDeviceToHost, c->stream));
+        if (cams->cam_tags && total) HIP_TRY(hipMemcpyAsync(cams->cam_tags, d_tags, 4 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SDM_OK;
 }
 
