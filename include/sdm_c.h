@@ -738,6 +738,98 @@ int sdm_vmap_get_obs_info(sdm_ctx *ctx, sdm_vmap_obs_info *info);
 int sdm_vmap_fetch_observations(sdm_ctx *ctx, long long first, long long count, sdm_vmap_observations *out);
 int sdm_vmap_fetch_cameras(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
                            sdm_vmap_cameras *cams);
+/* Classification on the persistent map: a rule over the per-entry state decides on the device which entries are surface,
+ * every entry keeps a persistent `published` flag, and every sdm_vmap_classify reports exactly which ids became accepted
+ * (the consumer emits `new point` for them) and which were retracted (`del point`).  The recipe is: integrate a block,
+ * observe it, carve it, classify; only the delta crosses the link.  Nothing in the reference does this; the semantics
+ * below are this library's (tests/vmap_class_np.py restates them in NumPy).  Requires an open map.
+ *   - State: every entry carries `published`, one byte, 0 or 1.  It is 0 when the entry is created and 0 after
+ *     sdm_vmap_clear; it survives table rehashes and record growth; sdm_vmap_close and sdm_destroy free it.  No other
+ *     call reads or writes it.  Classification removes nothing from the map: it only labels entries.
+ *   - Inputs of entry id: the multiplicity and the stored sigma of its record; ncam, the length of its observation list
+ *     (0 if no sdm_vmap_observe has run); crossings and ends (both 0 if no sdm_vmap_carve has run).
+ *   - Rule (sdm_vmap_rule, plain integers and one float).  The LOCAL tests pass iff all of
+ *         multiplicity >= min_multiplicity,  ncam >= min_cameras,  ends >= min_ends,
+ *         crossings * ratio_den <= ends * ratio_num,  key(sigma) <= key(max_sigma)
+ *     hold.  The ratio test compares the exact integer products (128 bits on the device; nothing wraps).  key() is
+ *     sdm_extract_points_voxel's total order on float bit patterns (negatives, -0, +0, positives, +Inf, then the NaNs
+ *     with the sign bit clear; NaNs with the sign bit set come first): every pattern has a place, so a NaN max_sigma is a
+ *     defined threshold.  Every compare is an integer compare: the result has no rounding.
+ *   - NEIGHBOUR test: nb(id) = the number of the 26 cells adjacent (Chebyshev distance 1) to the entry's cell that hold an
+ *     entry whose LOCAL tests pass.  A cell with a coordinate outside [-2^20, 2^20) holds nothing.  The entry's cell is
+ *     floorf(xyz_k * inv) of its record, as sdm_vmap_integrate forms it.
+ *   - passing(id) = LOCAL && nb(id) >= min_neighbours.  min_neighbours == 0 makes no neighbour probe.  passing does not
+ *     depend on published: it is a pure function of the map, the evidence, the log and the rule.
+ *   - Delta (sdm_vmap_class_delta): examined = M; accepted = entries with passing && !published; retracted = entries with
+ *     !passing && published; accepted_ids and retracted_ids list those ids in ascending order; published_total = entries
+ *     published after the call.  commit != 0: the listed entries flip their flag.  commit == 0: the lists and counts are
+ *     returned and no state changes (published_total is then the count before the call).  The id pointers follow
+ *     on_device (4-byte aligned there); either may be NULL, which gives counts only, and its capacity is then ignored.
+ *   - Capacity: accepted > accepted_capacity with accepted_ids != NULL is SDM_EINVAL, and so is retracted >
+ *     retracted_capacity with retracted_ids != NULL: the counts are filled, neither array is written and no flag changes
+ *     (sdm_voxel_cameras' cam_total > cam_capacity contract).  The caller sizes the arrays and calls again.
+ *   - Invariants.  C1: after a committing call, classifying again with the same rule and an unchanged map gives
+ *     accepted = retracted = 0.  C2: with rules A then B, both committing, B's accepted_ids = {passing_B \ passing_A} and its
+ *     retracted_ids = {passing_A \ passing_B}.  C3: the flags after any sequence of committing calls equal passing under
+ *     the last rule; entries created after that call read 0.  C4: a call changes no record, id, evidence counter or
+ *     observation, no field of sdm_vmap_get_info or sdm_vmap_get_obs_info, and no plane, flag, list or counter of the
+ *     engine.  C5: every output is bitwise the same from run to run, whatever the table layout.
+ * sdm_vmap_fetch_published returns the flags as u8 for entries first .. first + count - 1 (ids == NULL) or ids[0 .. count)
+ * (first must be 0; ids and out follow on_device, ids 4-byte aligned there), count <= capacity; zeros before the first
+ * classify.  sdm_vmap_get_class_info: published = entries whose flag is set, calls = committing sdm_vmap_classify calls
+ * since open / clear.
+ * Errors, all raised before any flag changes (a refused call leaves every info and every full fetch as it was):
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: NULL ctx, rule or delta; ratio_den == 0; min_neighbours outside 0 .. 26; a negative capacity; a misaligned
+ *     device pointer; the capacity case above; the fetch errors exactly as sdm_vmap_fetch's (count < 0, count > capacity, a
+ *     range beyond M, an id >= M, first != 0 with ids, a misaligned device pointer, no destination).
+ *   SDM_EHIP: an allocation failure -- everything is allocated before anything is written.
+ * On an argument or state refusal the outs of the delta are 0; in the capacity case all four are filled (published_total
+ * with the count before the call).
+ * Cost per sdm_vmap_classify: one pass over the M entries -- 4 B + 8 B + 4 B + 16 B + 1 B read and 1 B of scratch written
+ * per entry -- then, with min_neighbours > 0, per LOCAL-passing entry 12 B of xyz and up to 26 read-only probes of the
+ * table (8 B keys; on a hit 4 B of id and 1 B of scratch), ended early once min_neighbours is reached; two scans over
+ * M / 2048 tile counts; one more pass over 2 B per entry that writes 4 B per listed id.  The pass is O(M) per call, not
+ * O(block), and the probes make it latency-bound.  One host wait for the counts, one for the end; with host id lists
+ * 4 B per listed id cross the link, and nothing else does.
+ * Memory: 1 B per record of capacity, allocated at the first classify, plus 1 B per entry of per-call scratch.
+ * Limits: the pass is O(M) per call on the device; there is no hysteresis -- an entry whose evidence hovers at a threshold
+ * is accepted and retracted again and again, and damping that is the consumer's; the flags go stale with sdm_set_pose
+ * exactly as the evidence does (remedy: sdm_vmap_clear, then integrate, observe, carve and classify the resident slots
+ * again); one rank only. */
+typedef struct {
+    unsigned min_multiplicity;
+    unsigned min_cameras;
+    unsigned long long min_ends;
+    unsigned ratio_num;          /* crossings * ratio_den <= ends * ratio_num */
+    unsigned ratio_den;          /* >= 1 */
+    float max_sigma;             /* compared under key(); any bit pattern */
+    int min_neighbours;          /* 0 .. 26; 0: no neighbour probe */
+} sdm_vmap_rule;
+typedef struct {
+    unsigned *accepted_ids;        /* in: [accepted_capacity] or NULL */
+    unsigned *retracted_ids;       /* in: [retracted_capacity] or NULL */
+    long long accepted_capacity;   /* in */
+    long long retracted_capacity;  /* in */
+    int on_device;                 /* in: 1: both id arrays are device memory of this context's GPU (4-byte aligned) */
+    long long examined;            /* out: M */
+    long long accepted;            /* out */
+    long long retracted;           /* out */
+    long long published_total;     /* out: entries published after the call */
+} sdm_vmap_class_delta;
+typedef struct {
+    long long published;       /* entries whose flag is set */
+    long long calls;           /* committing sdm_vmap_classify calls since open / clear */
+} sdm_vmap_class_info;
+typedef struct {
+    unsigned char *published;  /* [capacity] */
+    long long capacity;
+    int on_device;             /* published (and ids) are device memory of this context's GPU (ids: 4-byte aligned) */
+} sdm_vmap_published;
+int sdm_vmap_classify(sdm_ctx *ctx, const sdm_vmap_rule *rule, int commit, sdm_vmap_class_delta *delta);
+int sdm_vmap_get_class_info(sdm_ctx *ctx, sdm_vmap_class_info *info);
+int sdm_vmap_fetch_published(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
+                             sdm_vmap_published *out);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -112,6 +112,29 @@ class VmapObsInfo(C.Structure):
                 ("rehashes", C.c_longlong)]
 
 
+class VmapRule(C.Structure):
+    """sdm_vmap_rule"""
+    _fields_ = [("min_multiplicity", C.c_uint), ("min_cameras", C.c_uint), ("min_ends", C.c_ulonglong),
+                ("ratio_num", C.c_uint), ("ratio_den", C.c_uint), ("max_sigma", C.c_float), ("min_neighbours", C.c_int)]
+
+
+class VmapClassDelta(C.Structure):
+    """sdm_vmap_class_delta"""
+    _fields_ = [("accepted_ids", C.c_void_p), ("retracted_ids", C.c_void_p), ("accepted_capacity", C.c_longlong),
+                ("retracted_capacity", C.c_longlong), ("on_device", C.c_int), ("examined", C.c_longlong),
+                ("accepted", C.c_longlong), ("retracted", C.c_longlong), ("published_total", C.c_longlong)]
+
+
+class VmapClassInfo(C.Structure):
+    """sdm_vmap_class_info"""
+    _fields_ = [("published", C.c_longlong), ("calls", C.c_longlong)]
+
+
+class VmapPublished(C.Structure):
+    """sdm_vmap_published"""
+    _fields_ = [("published", C.c_void_p), ("capacity", C.c_longlong), ("on_device", C.c_int)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -132,6 +155,11 @@ VMAP_CARVE_OUTS = ("plain_total", "rays_total", "rays_skipped", "cells_visited",
 # sdm_vmap_fetch_observations fields, and the outs of sdm_vmap_observe
 VMAP_OBSERVATION_FIELDS = {"entry": np.uint32, "tag": np.int32}
 VMAP_OBSERVE_OUTS = ("plain_total", "unmapped", "candidates", "first_created", "created")
+# the fields of sdm_vmap_rule with their defaults (every threshold at its laxest, ratio 1 / 1, any sigma up to +Inf), and
+# the outs of sdm_vmap_classify
+VMAP_RULE_DEFAULTS = {"min_multiplicity": 0, "min_cameras": 0, "min_ends": 0, "ratio_num": 1, "ratio_den": 1,
+                      "max_sigma": float("inf"), "min_neighbours": 0}
+VMAP_CLASS_OUTS = ("examined", "accepted", "retracted", "published_total")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -204,6 +232,9 @@ SYMBOLS = [
     ("sdm_vmap_get_obs_info", C.c_int, [_ctx, C.POINTER(VmapObsInfo)]),
     ("sdm_vmap_fetch_observations", C.c_int, [_ctx, C.c_longlong, C.c_longlong, C.POINTER(VmapObservations)]),
     ("sdm_vmap_fetch_cameras", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(VmapCameras)]),
+    ("sdm_vmap_classify", C.c_int, [_ctx, C.POINTER(VmapRule), C.c_int, C.POINTER(VmapClassDelta)]),
+    ("sdm_vmap_get_class_info", C.c_int, [_ctx, C.POINTER(VmapClassInfo)]),
+    ("sdm_vmap_fetch_published", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(VmapPublished)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1190,6 +1221,87 @@ class Engine:
         if out.get("cam_tags") is not None:
             res["cam_tags"] = out["cam_tags"][:total]
         return res
+
+    def vmap_classify(self, rule, commit=True, ids=True):
+        """Classifies the voxel map's entries on the device (sdm_vmap_classify).  rule: a dict with any of
+        min_multiplicity, min_cameras, min_ends, ratio_num, ratio_den, max_sigma, min_neighbours (VMAP_RULE_DEFAULTS
+        fills the rest).  Returns {"examined", "accepted", "retracted", "published_total"} and
+        "accepted_ids" / "retracted_ids" (uint32, ascending): the entries that pass and are not published, and those
+        published that no longer pass.  commit: the listed entries flip their `published` flag; False: nothing changes.
+        ids: True -- arrays are made here (sized by the published count: accepted <= M - published, retracted <=
+        published); False -- counts only; or {"accepted_ids": dest, "retracted_ids": dest}, either or both, each a uint32
+        array (pageable, or pinned from host_alloc) or a torch device tensor of 4-byte elements.  A destination too small
+        raises SdmError with .accepted and .retracted; no flag has changed then."""
+        for f in rule:
+            if f not in VMAP_RULE_DEFAULTS:
+                raise ValueError("unknown rule field %r" % (f,))
+        vals = dict(VMAP_RULE_DEFAULTS)
+        vals.update(rule)
+        r = VmapRule()
+        for f in VMAP_RULE_DEFAULTS:
+            setattr(r, f, float(vals[f]) if f == "max_sigma" else int(vals[f]))
+        d = VmapClassDelta()
+        dests = {}
+        if ids is True:
+            m, pub = self.vmap_info()["voxels"], self.vmap_class_info()["published"]
+            dests = {"accepted_ids": np.empty(max(m - pub, 1), np.uint32), "retracted_ids": np.empty(max(pub, 1), np.uint32)}
+        elif ids is not False and ids is not None:
+            for f, a in ids.items():
+                if f not in ("accepted_ids", "retracted_ids"):
+                    raise ValueError("unknown id list %r" % (f,))
+                if a is not None:
+                    dests[f] = a
+        kinds = set()
+        for f, a in dests.items():
+            ptr, cap = self._dest(f, a, np.uint32, 1, kinds)
+            setattr(d, f, ptr)
+            setattr(d, f.replace("ids", "capacity"), cap)
+        if len(kinds) > 1:
+            raise ValueError("the id lists mix host arrays and device tensors")
+        d.on_device = 1 if kinds == {"device"} else 0
+        rc = self.lib.sdm_vmap_classify(self.ctx, C.byref(r), 1 if commit else 0, C.byref(d))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.accepted, e.retracted = int(d.accepted), int(d.retracted)
+            raise e
+        res = {f: int(getattr(d, f)) for f in VMAP_CLASS_OUTS}
+        for f, a in dests.items():
+            res[f] = a[:res[f[:-4]]]
+        return res
+
+    def vmap_class_info(self):
+        """{"published", "calls"} of the classification (sdm_vmap_get_class_info)"""
+        info = VmapClassInfo()
+        self._check(self.lib.sdm_vmap_get_class_info(self.ctx, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in VmapClassInfo._fields_}
+
+    def vmap_fetch_published(self, ids=None, first=0, count=None, out=None):
+        """The `published` flags of the voxel map's entries (sdm_vmap_fetch_published), selected as vmap_fetch selects:
+        uint8[m], zeros before the first vmap_classify.  out: a preallocated uint8 array (pageable, or pinned from
+        host_alloc) or a torch device tensor of 1-byte elements."""
+        kinds = set()
+        idp = None
+        if ids is not None:
+            if isinstance(ids, np.ndarray) or not getattr(ids, "is_cuda", False):
+                ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+            idp, nid = self._dest("ids", ids, np.uint32, 1, kinds)
+            if count is None:
+                count = nid
+            elif count > nid:
+                raise ValueError("ids: fewer than count")
+        elif count is None:
+            count = max(self.vmap_info()["voxels"] - int(first), 0)
+        if out is None:
+            if kinds == {"device"}:
+                raise ValueError("device ids need a device destination in out")
+            out = np.empty(max(int(count), 1), np.uint8)
+        vp = VmapPublished()
+        vp.published, vp.capacity = self._dest("published", out, np.uint8, 1, kinds)
+        if len(kinds) > 1:
+            raise ValueError("ids and out mix host arrays and device tensors")
+        vp.on_device = 1 if kinds == {"device"} else 0
+        self._check(self.lib.sdm_vmap_fetch_published(self.ctx, idp, int(first), int(count), C.byref(vp)))
+        return out[:count]
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

@@ -37,6 +37,7 @@
 #include "sdm_vmap.h"
 #include "sdm_vmap_carve.h"
 #include "sdm_vmap_obs.h"
+#include "sdm_vmap_class.h"
 
 using namespace sdm;
 
@@ -306,6 +307,12 @@ struct sdm_ctx {
             unsigned char* h_pin = nullptr;
             size_t pin_bytes = 0;
         } obs;
+        // the classification (sdm_vmap_classify, sdm_vmap_class.h): one `published` byte per record of capacity, made at
+        // the first classify and grown with the records; a call's scratch, staging and pinned totals are the map's
+        struct Cls {
+            unsigned char* d_pub = nullptr;  // [rec_cap], or null before the first classify (every flag reads 0)
+            long long published = 0, calls = 0;
+        } cls;
     } vmap;
 
     // resident ORB observations (sdm_upload_observations*, sdm_priors.h): nothing is allocated before the first upload
@@ -1176,6 +1183,7 @@ void sdm_destroy(sdm_ctx* c)
     (void)hipFree(c->vmap.obs.d_scratch);
     (void)hipFree(c->vmap.obs.d_out);
     (void)hipHostFree(c->vmap.obs.h_pin);
+    (void)hipFree(c->vmap.cls.d_pub);
     (void)hipHostFree(c->h_vcam);
     (void)hipHostFree(c->h_ext);
     (void)hipFree(c->obs.ids);
@@ -2885,6 +2893,20 @@ static int vmap_make_obs_entries(sdm_ctx* c, long long cap, unsigned char** bloc
     return SDM_OK;
 }
 
+// the published flags of `cap` entries, all 0
+static int vmap_make_published(sdm_ctx* c, long long cap, unsigned char** block)
+{
+    const size_t b = (size_t)std::max(cap, 1ll);
+    HIP_TRY(hipMalloc((void**)block, b));
+    const hipError_t e = hipMemsetAsync(*block, 0, b, c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(*block);
+        *block = nullptr;
+        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    return SDM_OK;
+}
+
 static void vmap_free(sdm_ctx* c)
 {
     sdm_ctx::Vmap& v = c->vmap;
@@ -2900,6 +2922,7 @@ static void vmap_free(sdm_ctx* c)
     (void)hipFree(v.obs.d_scratch);
     (void)hipFree(v.obs.d_out);
     (void)hipHostFree(v.obs.h_pin);
+    (void)hipFree(v.cls.d_pub);
     v = sdm_ctx::Vmap{};
 }
 
@@ -2949,7 +2972,9 @@ int sdm_vmap_clear(sdm_ctx* c)
         HIP_TRY(hipMemsetAsync(v.obs.d_ent, 0xff, b4, c->stream));
         HIP_TRY(hipMemsetAsync(v.obs.d_ent + b4, 0, b4, c->stream));
     }
+    if (v.cls.d_pub) HIP_TRY(hipMemsetAsync(v.cls.d_pub, 0, (size_t)v.rec_cap, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    v.cls.published = v.cls.calls = 0;
     v.M = v.points = v.dropped = v.calls = v.rehashes = 0;
     v.obs.E = v.obs.calls = v.obs.rehashes = 0;
     v.obs.seen.clear();
@@ -3031,9 +3056,20 @@ static int vmap_grow(sdm_ctx* c, long long need)
             (void)hipFree(evid);
             return rc;
         }
+        unsigned char* pub = nullptr;  // and the published flags: M entries copied, the rest 0
+        if (v.cls.d_pub && (rc = vmap_make_published(c, cap, &pub))) {
+            (void)hipFree(block);
+            (void)hipFree(evid);
+            (void)hipFree(ent);
+            return rc;
+        }
         const size_t m = (size_t)v.M;
         hipError_t e = hipSuccess;
-        if (ent) {
+        if (pub) {
+            if (m) e = hipMemcpyAsync(pub, v.cls.d_pub, m, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
+        }
+        if (ent && e == hipSuccess) {
             if (m) e = hipMemcpyAsync(nlast, v.obs.last_obs, 4 * m, hipMemcpyDeviceToDevice, c->stream);
             if (m && e == hipSuccess) e = hipMemcpyAsync(nncam, v.obs.ncam, 4 * m, hipMemcpyDeviceToDevice, c->stream);
             if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
@@ -3057,7 +3093,12 @@ static int vmap_grow(sdm_ctx* c, long long need)
             (void)hipFree(block);
             (void)hipFree(evid);
             (void)hipFree(ent);
+            (void)hipFree(pub);
             return fail(SDM_EHIP, std::string("voxel map records: ") + hipGetErrorString(e));
+        }
+        if (pub) {  // (waited for above, as the records are)
+            (void)hipFree(v.cls.d_pub);
+            v.cls.d_pub = pub;
         }
         if (ent) {  // (waited for above, as the records are)
             (void)hipFree(v.obs.d_ent);
@@ -3832,6 +3873,202 @@ int sdm_vmap_fetch_cameras(sdm_ctx* c, const unsigned* ids, long long first, lon
         if (cams->cam_tags && total) HIP_TRY(hipMemcpyAsync(cams->cam_tags, d_tags, 4 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDM_OK;
+}
+
+// ---- classification on the persistent voxel map (sdm_vmap_class.h) --------------------------------------------------------
+int sdm_vmap_classify(sdm_ctx* c, const sdm_vmap_rule* rule, int commit, sdm_vmap_class_delta* delta)
+{
+    if (delta) delta->examined = delta->accepted = delta->retracted = delta->published_total = 0;
+    if (!c || !rule || !delta) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (rule->ratio_den == 0) return fail(SDM_EINVAL, "ratio_den must be at least 1");
+    if (rule->min_neighbours < 0 || rule->min_neighbours > 26) return fail(SDM_EINVAL, "min_neighbours outside 0 .. 26");
+    unsigned* acc_dst = delta->accepted_ids;
+    unsigned* ret_dst = delta->retracted_ids;
+    if ((acc_dst && delta->accepted_capacity < 0) || (ret_dst && delta->retracted_capacity < 0))
+        return fail(SDM_EINVAL, "negative capacity");
+    const bool dev = delta->on_device != 0;
+    if (dev && ((uintptr_t)acc_dst | (uintptr_t)ret_dst) % 4)
+        return fail(SDM_EINVAL, "device buffer not aligned (accepted_ids, retracted_ids: 4 B)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+
+    // the flags, the scratch and the pinned totals: everything but the id staging, which follows the counts
+    const long long M = v.M;
+    const long long vt = (M + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t flag_b = ext_align((size_t)std::max(M, 1ll)), tcnt_b = ext_align(4 * (size_t)std::max(vt, 1ll)),
+                 toff_b = ext_align(4 * (size_t)(vt + 1)), blk_b = ext_align(8 * (size_t)vb);
+    int rc;
+    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + flag_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b))) return rc;
+    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256))) return rc;
+    if (!v.cls.d_pub && (rc = vmap_make_published(c, v.rec_cap, &v.cls.d_pub))) return rc;
+    delta->examined = M;
+    delta->published_total = v.cls.published;
+    if (M == 0) {  // nothing to examine
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (commit) v.cls.calls++;
+        return SDM_OK;
+    }
+    unsigned char* p = v.d_scratch;
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {accepted, retracted, published_total}
+    p += 512;
+    unsigned char* d_flag = p;
+    p += flag_b;
+    unsigned* d_cnt_acc = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_cnt_ret = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off_acc = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned* d_off_ret = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum_acc = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_acc = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_bsum_ret = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_ret = reinterpret_cast<unsigned long long*>(p);
+
+    VclsRule r;
+    r.min_multiplicity = rule->min_multiplicity;
+    r.min_cameras = rule->min_cameras;
+    r.min_ends = rule->min_ends;
+    r.ratio_num = rule->ratio_num;
+    r.ratio_den = rule->ratio_den;
+    unsigned bits;
+    std::memcpy(&bits, &rule->max_sigma, 4);
+    r.max_sigma_key = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);  // f2key
+    r.min_neighbours = rule->min_neighbours;
+    VclsIn in;
+    in.multiplicity = v.rec.multiplicity;
+    in.rho_sigma = v.rec.rho_sigma;
+    in.ncam = v.obs.ncam;
+    in.crossings = v.crossings;
+    in.ends = v.ends;
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long eblocks = (M + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < eblocks; b0 += per)
+        hipLaunchKernelGGL(k_vcls_local, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in, r, M, b0 * BLOCK,
+                           d_flag);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vcls_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec.xyz, v.inv,
+                           r.min_neighbours, M, t0, d_flag, v.cls.d_pub, d_cnt_acc, d_cnt_ret);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_acc, vt, d_off_acc, d_bsum_acc);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_acc, (int)vb, d_boff_acc);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_ret, vt, d_off_ret, d_bsum_ret);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_ret, (int)vb, d_boff_ret);
+    hipLaunchKernelGGL(k_vcls_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_acc, d_boff_acc, d_off_ret, d_boff_ret,
+                       (unsigned long long)v.cls.published, commit, d_tot);
+    HIP_TRY(hipGetLastError());
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 24, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the one wait for the counts
+    const long long accepted = (long long)h_tot[0], retracted = (long long)h_tot[1];
+    delta->accepted = accepted;
+    delta->retracted = retracted;
+    if (acc_dst && accepted > delta->accepted_capacity)
+        return fail(SDM_EINVAL, "accepted_capacity " + std::to_string(delta->accepted_capacity) + " < " + std::to_string(accepted) +
+                                    " accepted entries (the counts are filled)");
+    if (ret_dst && retracted > delta->retracted_capacity)
+        return fail(SDM_EINVAL, "retracted_capacity " + std::to_string(delta->retracted_capacity) + " < " + std::to_string(retracted) +
+                                    " retracted entries (the counts are filled)");
+    const bool list_acc = acc_dst && accepted, list_ret = ret_dst && retracted;
+    if (commit ? accepted + retracted > 0 : (list_acc || list_ret)) {
+        unsigned *d_acc = list_acc ? acc_dst : nullptr, *d_ret = list_ret ? ret_dst : nullptr;
+        const size_t acc_b = list_acc ? ext_align(4 * (size_t)accepted) : 0;
+        if (!dev && (list_acc || list_ret)) {  // (no flag has changed yet: a failure here leaves the state as it was)
+            if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, acc_b + 4 * (size_t)(list_ret ? retracted : 0)))) return rc;
+            if (list_acc) d_acc = reinterpret_cast<unsigned*>(v.d_out);
+            if (list_ret) d_ret = reinterpret_cast<unsigned*>(v.d_out + acc_b);
+        }
+        for (long long t0 = 0; t0 < vt; t0 += per)
+            hipLaunchKernelGGL(k_vcls_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, d_flag, v.cls.d_pub,
+                               commit, M, t0, d_off_acc, d_boff_acc, d_off_ret, d_boff_ret, d_acc, d_ret);
+        HIP_TRY(hipGetLastError());
+        if (!dev) {
+            if (list_acc) HIP_TRY(hipMemcpyAsync(acc_dst, d_acc, 4 * (size_t)accepted, hipMemcpyDeviceToHost, c->stream));
+            if (list_ret) HIP_TRY(hipMemcpyAsync(ret_dst, d_ret, 4 * (size_t)retracted, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (commit) {
+        v.cls.published = (long long)h_tot[2];
+        v.cls.calls++;
+    }
+    delta->published_total = v.cls.published;
+    return SDM_OK;
+}
+
+int sdm_vmap_get_class_info(sdm_ctx* c, sdm_vmap_class_info* info)
+{
+    if (!c || !info) return fail(SDM_EINVAL, "null argument");
+    const sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    std::memset(info, 0, sizeof(*info));
+    info->published = v.cls.published;
+    info->calls = v.cls.calls;
+    return SDM_OK;
+}
+
+int sdm_vmap_fetch_published(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_vmap_published* out)
+{
+    if (!c || !out) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (!out->published) return fail(SDM_EINVAL, "no output requested");
+    if (count < 0 || out->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
+    if (count > out->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
+    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
+        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
+    const bool dev = out->on_device != 0;
+    if (dev && (uintptr_t)ids % 4) return fail(SDM_EINVAL, "device buffer not aligned (ids: 4 B)");
+    if (ids && !dev)
+        for (long long j = 0; j < count; j++)
+            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (count == 0) return SDM_OK;
+    const size_t m = (size_t)count;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const unsigned char* src = v.cls.d_pub;  // (null: no classify has run, every flag reads 0)
+    unsigned* h_bad = nullptr;
+    if (!ids) {
+        if (src) src += first;
+    } else {
+        // ids, the flag and -- for a host destination -- one dense region
+        const size_t ids_b = ext_align(4 * m);
+        int rc;
+        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, ids_b + 256 + (dev ? 0 : ext_align(m)))) ||
+            (rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256)))
+            return rc;
+        unsigned char* b = v.d_out;
+        const unsigned* d_ids = ids;
+        unsigned* d_bad = reinterpret_cast<unsigned*>(b + ids_b);
+        h_bad = reinterpret_cast<unsigned*>(v.h_pin);
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(b, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
+            d_ids = reinterpret_cast<const unsigned*>(b);
+        }
+        unsigned char* dst = dev ? out->published : b + ids_b + 256;
+        HIP_TRY(hipMemsetAsync(d_bad, 0, 4, c->stream));
+        const long long per = (1ll << 31) / BLOCK;
+        const long long blocks = (count + BLOCK - 1) / BLOCK;
+        for (long long b0 = 0; b0 < blocks; b0 += per)
+            hipLaunchKernelGGL(k_vcls_gather, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, src, d_ids, count,
+                               b0 * BLOCK, (unsigned)v.M, dst, d_bad);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+        src = dst;
+    }
+    if (!ids || !dev) {  // one copy of exactly count flags (zeros before the first classify)
+        if (src) HIP_TRY(hipMemcpyAsync(out->published, src, m, kind, c->stream));
+        else if (dev) HIP_TRY(hipMemsetAsync(out->published, 0, m, c->stream));
+        else std::memset(out->published, 0, m);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
     return SDM_OK;
 }
 
