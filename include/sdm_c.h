@@ -532,12 +532,13 @@ int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, in
  * launch (ids form).
  * Limits: a keyframe's contribution cannot be removed; stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
  * integrate the resident slots again); free-space evidence is kept per entry by sdm_vmap_carve and the camera
- * lists by sdm_vmap_observe (both below); one rank only. */
+ * lists by sdm_vmap_observe (both below); one rank only per map: the maps of several ranks, a saved map or a map of
+ * another voxel_size come in through sdm_vmap_import (below). */
 typedef struct {
     long long voxels;       /* M */
     long long points;       /* mergeable points integrated */
     long long dropped;      /* unmergeable points met */
-    long long calls;        /* successful sdm_vmap_integrate calls since open / clear */
+    long long calls;        /* successful sdm_vmap_integrate and sdm_vmap_import calls since open / clear */
     long long table_slots;
     long long rehashes;     /* table growths since open / clear */
     float voxel_size;
@@ -606,7 +607,8 @@ int sdm_vmap_fetch(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long l
  * Memory: 16 B per record of capacity, allocated at the first carve.  Two host waits: T, the end (with the totals).
  * Limits: evidence is relative to the entries present at each carve, so -- unlike the map itself -- it is NOT invariant
  * under re-splitting integrates and carves against each other; carving the same slots twice counts twice; the counters go
- * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed; one rank only. */
+ * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed; one rank only: the
+ * counters do not travel with sdm_vmap_import (below) -- carve on the merged map. */
 typedef struct {
     int end_margin;            /* in: >= 0 */
     int max_steps;             /* in: 1 .. SDM_FREESPACE_MAX_STEPS */
@@ -703,7 +705,8 @@ int sdm_vmap_fetch_evidence(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*
  * neighbours reserves far more than it creates -- and they never shrink before sdm_vmap_close (sdm_vmap_clear keeps the
  * capacity); the lists go stale with sdm_set_pose exactly as the stored xyz do (remedy: sdm_vmap_clear, integrate and
  * observe the resident slots again); an observation cannot be removed: removing one and shrinking the camera lists on
- * the persistent map remain later work; one rank only. */
+ * the persistent map remain later work; one rank only per log: the logs of several ranks merge through
+ * sdm_vmap_import_observations (below). */
 typedef struct {
     long long plain_total;     /* out: T */
     long long unmapped;        /* out: plain points without an entry */
@@ -727,7 +730,7 @@ typedef struct {
 } sdm_vmap_cameras;
 typedef struct {
     long long observations;    /* E */
-    long long calls;           /* successful sdm_vmap_observe calls since open / clear */
+    long long calls;           /* successful sdm_vmap_observe and sdm_vmap_import_observations calls since open / clear */
     long long table_slots;     /* slots of the observation set */
     long long rehashes;        /* its growths since open / clear */
 } sdm_vmap_obs_info;
@@ -796,7 +799,7 @@ int sdm_vmap_fetch_cameras(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/
  * Limits: the pass is O(M) per call on the device; there is no hysteresis -- an entry whose evidence hovers at a threshold
  * is accepted and retracted again and again, and damping that is the consumer's; the flags go stale with sdm_set_pose
  * exactly as the evidence does (remedy: sdm_vmap_clear, then integrate, observe, carve and classify the resident slots
- * again); one rank only. */
+ * again); one rank only: the flags do not travel with sdm_vmap_import (below) -- classify the merged map. */
 typedef struct {
     unsigned min_multiplicity;
     unsigned min_cameras;
@@ -830,6 +833,93 @@ int sdm_vmap_classify(sdm_ctx *ctx, const sdm_vmap_rule *rule, int commit, sdm_v
 int sdm_vmap_get_class_info(sdm_ctx *ctx, sdm_vmap_class_info *info);
 int sdm_vmap_fetch_published(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long long first, long long count,
                              sdm_vmap_published *out);
+/* Importing into the persistent map: sdm_vmap_fetch writes an entry's fields out, sdm_vmap_import reads them back in --
+ * into ANY open map.  That is how the maps of several ranks become one, how a saved map is restored, and how a map is
+ * re-binned at another voxel_size.  Nothing in the reference does this; the semantics below are this library's
+ * (tests/vmap_import_np.py restates them in NumPy).  Requires an open map; voxel_size, inv, the cell floorf(xyz_k * inv),
+ * mergeability and key(sigma) are sdm_vmap_integrate's, with the DESTINATION map's voxel_size.
+ *   - Sources: `src` and `extra` are the two structs sdm_vmap_fetch writes, read here.  src->xyz and src->rho_sigma are
+ *     required (count > 0); src->pixel, src->intensity and extra->tag may be NULL and then read as 0; extra->multiplicity
+ *     NULL (or extra NULL) reads as 1 for every record; extra->epoch is ignored.  src->on_device covers every source
+ *     pointer, aligned there as sdm_vmap_fetch asks (4 B; rho_sigma: 8 B).  src->capacity >= count.  The sources are only
+ *     read.
+ *   - Call number: the import is call number c of the map: `calls` counts successful sdm_vmap_integrate and
+ *     sdm_vmap_import calls alike, from 1 since open or clear.
+ *   - Importing: the records r = 0 .. R-1, R = count, with multiplicity m_r, are processed as if one by one in increasing r:
+ *       * a record whose xyz is unmergeable or whose m_r is 0 adds 1 to `dropped`, is not stored, and gets
+ *         dst_ids[r] = 0xFFFFFFFF;
+ *       * a record whose voxel has no entry creates entry id = M from its copied bits: xyz, pixel, rho_sigma, intensity,
+ *         tag, multiplicity = m_r, epoch = c; then M += 1;
+ *       * otherwise multiplicity = min(2^32 - 1, multiplicity + m_r), and if key(sigma_r) < the key of the entry's stored
+ *         sigma, STRICTLY, the record replaces the stored one (its five fields) and epoch = c.
+ *     dst_ids[r] is the entry that holds record r's voxel after the call.  `points` adds the sum of m_r over the stored
+ *     records (a 64-bit sum); the map's `dropped` adds the call's.
+ *   - Delta (sdm_vmap_import_delta): total = R; dropped; first_created = M before the call; created = entries appended,
+ *     with ids first_created .. first_created + created - 1 in the order of their first record; updated = entries with
+ *     id < first_created whose epoch became c; updated_ids lists those in ascending order of the r of the entry's final
+ *     winner in this call, as sdm_vmap_integrate orders by g.  dst_ids and updated_ids follow delta->on_device.
+ *   - Invariants.  I1: importing a range in one call or in any split into consecutive calls leaves byte-identical maps
+ *     except `epoch` and `calls`.  I2: with B a map built from the clouds Q and A a map of the same voxel_size built from
+ *     the clouds P, importing the full sdm_vmap_fetch of B into A gives exactly the map of integrating P then Q into one
+ *     map -- every field but `epoch`, `calls` and `dropped` ("smallest key(sigma) wins, ties to the earlier, ids by first
+ *     appearance, multiplicities add saturating" is associative over consecutive groups).  I3: importing a map's own full
+ *     fetch into an empty map of the same voxel_size reproduces it, ids included (dst_ids[r] = r; `points` is the sum of
+ *     the fetched multiplicities, which is the source's `points` unless a multiplicity had saturated).
+ * sdm_vmap_import_observations does the same for the log: pairs k = 0 .. P-1, P = count, are processed as if in
+ * increasing k.  The pair's entry is entry[k], or entry_map[entry[k]] when entry_map != NULL (an entry[k] >= map_count
+ * is rejected): pass a source rank's log with sdm_vmap_import's dst_ids as the map and no host gather is needed -- the
+ * dropped records' 0xFFFFFFFF falls out by itself.  A pair whose resolved entry is >= M or whose tag is < 0 adds 1 to
+ * `rejected` and contributes nothing: a count, like `unmapped` in sdm_vmap_observe, never a refusal.  A pair not yet
+ * stored is appended at index E; then E += 1.  Outs: total = P, rejected, first_created = E before the call, created.
+ * Invariants: any split into consecutive calls leaves the same log; importing the same pairs again creates nothing; every
+ * entry's camera list is independent of the order of the calls.  The map itself is only read.  sdm_vmap_get_obs_info's
+ * `calls` counts these calls too.
+ * Everything is integer or copied bits: every returned array is bitwise the same from run to run.
+ * Errors, all raised before the map or the log changes (a refused call leaves both infos, a full fetch and the log as
+ * they were; no refusal depends on device data):
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: a NULL ctx, src or io; count < 0; count > src->capacity; a NULL xyz, rho_sigma, entry or tag with
+ *     count > 0; a misaligned device pointer; updated_ids != NULL with updated_capacity < min(M, R), the a-priori bound on
+ *     `updated` (total and first_created are filled), or < 0; M + R > 2^30; map_count < 0; E + P > 2^30 (the bound of
+ *     sdm_vmap_observe's B).
+ *   SDM_EHIP: an allocation failure while growing -- growth is done before anything is inserted.
+ * On an argument or state refusal the outs are 0, except total and first_created once known.
+ * Changes no plane, flag, list or counter of the engine; evidence counters, observations and published flags of the
+ * existing entries survive the growth an import forces, and a created entry's read 0.
+ * Cost per sdm_vmap_import, outside a growth proportional to R: host sources are staged through the map's scratch (33 B
+ * per record with every field); per record 24 B read, one probe of the table with four integer atomics (a 64-bit
+ * compare-and-swap, a 64-bit min, a 32-bit min and a 32-bit compare-and-swap loop that adds m_r and clamps at 2^32 - 1,
+ * so the per-call count stays 32 bits and a table slot 28 B) and 4 B of table position; three more passes over those 4 B
+ * and the table fields; 4 B of dst_ids per record and a 37 B record per created or updated entry.  Two host waits: the
+ * counts, the end.  Per sdm_vmap_import_observations: 8 B per pair read (12 B with a map), one probe of the set with a
+ * 64-bit compare-and-swap and a 64-bit min, two more passes over 4 B per pair; per created pair a 12 B log entry.  The
+ * tags of device pairs are copied back once (4 B per pair) to keep sdm_vmap_fetch_cameras' bound on a list's length: every
+ * tag >= 0 of a call counts as a distinct tag observed for that refusal, a rejected pair's too, so the bound can only be
+ * larger than the longest list.
+ * Two host waits.  Set and log are sized a priori for E + P.
+ * Limits: evidence counters and published flags do not travel: sdm_vmap_carve and sdm_vmap_classify run on the merged
+ * map, and evidence carved on one rank is relative to that rank's entries, so it does not add up across ranks; the
+ * records of several ranks reach one context through host or device buffers the caller moves -- there is no collective
+ * inside the call; a record cannot be removed. */
+typedef struct {
+    unsigned *dst_ids;            /* in: [count] or NULL; out: entry id of record r, 0xFFFFFFFF for a dropped one */
+    unsigned *updated_ids;        /* in: [updated_capacity] or NULL */
+    long long updated_capacity;   /* in */
+    int on_device;                /* in: 1: dst_ids and updated_ids are device memory (4-byte aligned) */
+    long long total;              /* out: R = count */
+    long long dropped, first_created, created, updated;   /* out */
+} sdm_vmap_import_delta;
+int sdm_vmap_import(sdm_ctx *ctx, const sdm_point_buffers *src, const sdm_vmap_fields *extra /* or NULL */,
+                    long long count, sdm_vmap_import_delta *delta /* or NULL */);
+typedef struct {
+    const unsigned *entry;        /* [count] */
+    const int *tag;               /* [count] */
+    const unsigned *entry_map;    /* [map_count] or NULL: the pair's entry is entry_map[entry[k]] */
+    long long map_count;
+    int on_device;                /* all three pointers, 4-byte aligned */
+    long long total, rejected, first_created, created;    /* out */
+} sdm_vmap_obs_import;
+int sdm_vmap_import_observations(sdm_ctx *ctx, long long count, sdm_vmap_obs_import *io);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

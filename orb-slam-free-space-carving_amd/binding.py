@@ -135,6 +135,20 @@ class VmapPublished(C.Structure):
     _fields_ = [("published", C.c_void_p), ("capacity", C.c_longlong), ("on_device", C.c_int)]
 
 
+class VmapImportDelta(C.Structure):
+    """sdm_vmap_import_delta"""
+    _fields_ = [("dst_ids", C.c_void_p), ("updated_ids", C.c_void_p), ("updated_capacity", C.c_longlong),
+                ("on_device", C.c_int), ("total", C.c_longlong), ("dropped", C.c_longlong), ("first_created", C.c_longlong),
+                ("created", C.c_longlong), ("updated", C.c_longlong)]
+
+
+class VmapObsImport(C.Structure):
+    """sdm_vmap_obs_import"""
+    _fields_ = [("entry", C.c_void_p), ("tag", C.c_void_p), ("entry_map", C.c_void_p), ("map_count", C.c_longlong),
+                ("on_device", C.c_int), ("total", C.c_longlong), ("rejected", C.c_longlong), ("first_created", C.c_longlong),
+                ("created", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -160,6 +174,9 @@ VMAP_OBSERVE_OUTS = ("plain_total", "unmapped", "candidates", "first_created", "
 VMAP_RULE_DEFAULTS = {"min_multiplicity": 0, "min_cameras": 0, "min_ends": 0, "ratio_num": 1, "ratio_den": 1,
                       "max_sigma": float("inf"), "min_neighbours": 0}
 VMAP_CLASS_OUTS = ("examined", "accepted", "retracted", "published_total")
+# the outs of sdm_vmap_import and sdm_vmap_import_observations
+VMAP_IMPORT_OUTS = ("total", "dropped", "first_created", "created", "updated")
+VMAP_OBS_IMPORT_OUTS = ("total", "rejected", "first_created", "created")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -235,6 +252,9 @@ SYMBOLS = [
     ("sdm_vmap_classify", C.c_int, [_ctx, C.POINTER(VmapRule), C.c_int, C.POINTER(VmapClassDelta)]),
     ("sdm_vmap_get_class_info", C.c_int, [_ctx, C.POINTER(VmapClassInfo)]),
     ("sdm_vmap_fetch_published", C.c_int, [_ctx, C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(VmapPublished)]),
+    ("sdm_vmap_import", C.c_int, [_ctx, C.POINTER(PointBuffers), C.POINTER(VmapFields), C.c_longlong,
+                                  C.POINTER(VmapImportDelta)]),
+    ("sdm_vmap_import_observations", C.c_int, [_ctx, C.c_longlong, C.POINTER(VmapObsImport)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1302,6 +1322,113 @@ class Engine:
         vp.on_device = 1 if kinds == {"device"} else 0
         self._check(self.lib.sdm_vmap_fetch_published(self.ctx, idp, int(first), int(count), C.byref(vp)))
         return out[:count]
+
+    def _like(self, kinds, like, n, dt):
+        """a destination of n elements where the sources are: a NumPy array, or a tensor on the device of `like`"""
+        if kinds == {"device"}:
+            import torch  # (a device tensor was passed in: torch is loaded)
+            return like.new_empty(max(n, 1), dtype=torch.int32)
+        return np.empty(max(n, 1), dt)
+
+    def vmap_import(self, records, dst_ids=True, updated=True):
+        """Merges records into the voxel map (sdm_vmap_import).  records: a dict as vmap_fetch returns it -- "xyz" and
+        "rho_sigma" required, "pixel", "intensity", "tag" optional (read as 0), "multiplicity" optional (read as 1),
+        "epoch" ignored -- of NumPy arrays or of torch tensors on this engine's GPU (all of one kind and one length).  Record r creates or
+        joins the entry of its voxel exactly as a plain point of vmap_integrate would, with its multiplicity.  Returns
+        {"total", "dropped", "first_created", "created", "updated"}, "dst_ids" (uint32[total]: the entry of each record,
+        0xFFFFFFFF for a dropped one) and "updated_ids" (uint32[updated]).  dst_ids / updated: True -- made here, where the
+        records are (device: int32 tensors holding the same bits); False -- not returned; or the destination (both of one
+        kind).  A refusal raises SdmError with .total and .first_created."""
+        known = dict(POINT_FIELDS)
+        known.update(VMAP_EXTRA_FIELDS)
+        for f in ("xyz", "rho_sigma"):
+            if records.get(f) is None:
+                raise ValueError("records: %r is required" % (f,))
+        pb, vf = PointBuffers(), VmapFields()
+        kinds = set()
+        count, like, keep = None, None, []
+        for f, a in records.items():
+            if f not in known:
+                raise ValueError("unknown voxel map field %r" % (f,))
+            if f == "epoch" or a is None:
+                continue
+            if isinstance(a, np.ndarray):
+                a = np.ascontiguousarray(a, dtype=known[f][0])
+            ptr, m = self._dest(f, a, known[f][0], known[f][1], kinds, 8 if f == "rho_sigma" else None)
+            setattr(vf if f in VMAP_EXTRA_FIELDS else pb, f, ptr)
+            keep.append(a)  # (a converted copy lives until the call returns)
+            if count is not None and m != count:
+                raise ValueError("records: %r holds %d records, the fields before it %d" % (f, m, count))
+            count = m
+            like = a
+        if len(kinds) > 1:
+            raise ValueError("records mix host arrays and device tensors")
+        pb.capacity = count
+        pb.on_device = 1 if kinds == {"device"} else 0
+        d = VmapImportDelta()
+        dk = set()
+        ids = self._like(kinds, like, count, np.uint32) if dst_ids is True else None if dst_ids is False else dst_ids
+        if ids is not None:
+            d.dst_ids, m = self._dest("dst_ids", ids, np.uint32, 1, dk)
+            if m < count:
+                raise ValueError("dst_ids: fewer than records")
+        upd = None
+        if updated is True:
+            upd = self._like(kinds, like, min(self.vmap_info()["voxels"], count), np.uint32)
+        elif updated is not False and updated is not None:
+            upd = updated
+        if upd is not None:
+            d.updated_ids, d.updated_capacity = self._dest("updated_ids", upd, np.uint32, 1, dk)
+        if len(dk) > 1:
+            raise ValueError("dst_ids and updated mix host arrays and device tensors")
+        d.on_device = 1 if dk == {"device"} else 0
+        rc = self.lib.sdm_vmap_import(self.ctx, C.byref(pb), C.byref(vf), int(count), C.byref(d))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.total, e.first_created = int(d.total), int(d.first_created)
+            raise e
+        res = {f: int(getattr(d, f)) for f in VMAP_IMPORT_OUTS}
+        if ids is not None:
+            res["dst_ids"] = ids[:count]
+        if upd is not None:
+            res["updated_ids"] = upd[:res["updated"]]
+        return res
+
+    def vmap_import_observations(self, entry, tag, entry_map=None):
+        """Merges (entry, tag) pairs into the observation log (sdm_vmap_import_observations).  entry uint32[P] and tag
+        int32[P] as vmap_fetch_observations returns them; with entry_map (uint32[map_count]) the pair's entry is
+        entry_map[entry[k]] -- pass another map's log with vmap_import's "dst_ids".  NumPy arrays, or torch tensors of
+        4-byte elements on this engine's GPU (all of one kind).  A pair whose entry is beyond the map (or the entry_map)
+        or whose tag is negative is counted in "rejected".  Returns {"total", "rejected", "first_created", "created"}:
+        the new pairs are log entries first_created .. first_created + created - 1."""
+        io = VmapObsImport()
+        kinds = set()
+        keep = []
+        for f, a, dt in (("entry", entry, np.uint32), ("tag", tag, np.int32), ("entry_map", entry_map, np.uint32)):
+            if a is None:
+                if f != "entry_map":
+                    raise ValueError("%s is required" % f)
+                continue
+            if isinstance(a, np.ndarray) or not getattr(a, "is_cuda", False):
+                a = np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(-1))
+            keep.append(a)
+            ptr, m = self._dest(f, a, dt, 1, kinds)
+            setattr(io, f, ptr)
+            if f == "entry_map":
+                io.map_count = m
+            elif f == "entry":
+                count = m
+            elif m != count:
+                raise ValueError("entry and tag: need the same length")
+        if len(kinds) > 1:
+            raise ValueError("entry, tag and entry_map mix host arrays and device tensors")
+        io.on_device = 1 if kinds == {"device"} else 0
+        rc = self.lib.sdm_vmap_import_observations(self.ctx, int(count), C.byref(io))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.total, e.first_created = int(io.total), int(io.first_created)
+            raise e
+        return {f: int(getattr(io, f)) for f in VMAP_OBS_IMPORT_OUTS}
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

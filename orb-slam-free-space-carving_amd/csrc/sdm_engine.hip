@@ -23,6 +23,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <new>
 #include <vector>
 
 #include "sdm_c.h"
@@ -38,6 +39,7 @@
 #include "sdm_vmap_carve.h"
 #include "sdm_vmap_obs.h"
 #include "sdm_vmap_class.h"
+#include "sdm_vmap_import.h"
 
 using namespace sdm;
 
@@ -4069,6 +4071,271 @@ int sdm_vmap_fetch_published(sdm_ctx* c, const unsigned* ids, long long first, l
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
+    return SDM_OK;
+}
+
+// ---- importing records and observations into the persistent voxel map (sdm_vmap_import.h) --------------------------------
+int sdm_vmap_import(sdm_ctx* c, const sdm_point_buffers* src, const sdm_vmap_fields* extra, long long count,
+                    sdm_vmap_import_delta* delta)
+{
+    if (delta) delta->total = delta->dropped = delta->first_created = delta->created = delta->updated = 0;
+    if (!c || !src) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (count < 0 || src->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
+    if (count > src->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
+    if (count > 0 && (!src->xyz || !src->rho_sigma)) return fail(SDM_EINVAL, "null source (xyz and rho_sigma are required)");
+    const int* s_tag = extra ? extra->tag : nullptr;
+    const unsigned* s_mult = extra ? extra->multiplicity : nullptr;
+    const bool dev = src->on_device != 0;
+    if (dev && (((uintptr_t)src->xyz | (uintptr_t)src->pixel | (uintptr_t)s_tag | (uintptr_t)s_mult) % 4 || (uintptr_t)src->rho_sigma % 8))
+        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel, tag, multiplicity: 4 B; rho_sigma: 8 B)");
+    unsigned* ids_dst = delta ? delta->dst_ids : nullptr;
+    unsigned* upd_dst = delta ? delta->updated_ids : nullptr;
+    if (upd_dst && delta->updated_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
+    if (delta && delta->on_device && ((uintptr_t)ids_dst | (uintptr_t)upd_dst) % 4)
+        return fail(SDM_EINVAL, "device buffer not aligned (dst_ids, updated_ids: 4 B)");
+    const long long R = count;
+    if (delta) delta->total = R, delta->first_created = v.M;
+    if (v.M + R > (1ll << 30)) return fail(SDM_EINVAL, "more than 2^30 entries and records: the voxel map's table would exceed 2^31 slots");
+    if (upd_dst && delta->updated_capacity < std::min(v.M, R))
+        return fail(SDM_EINVAL, "updated_capacity " + std::to_string(delta->updated_capacity) + " < min(entries, records) = " +
+                                    std::to_string(std::min(v.M, R)) + " (total and first_created filled)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (R == 0) {
+        v.calls++;
+        return SDM_OK;
+    }
+
+    // scratch, the staging of host sources and destinations, and growth: everything is allocated before anything is inserted
+    const size_t m = (size_t)R;
+    const long long vt = (R + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t where_b = ext_align(4 * m), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
+    const size_t blk_b = ext_align(8 * (size_t)vb);
+    size_t at = 512 + where_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b;
+    size_t xyz_off = 0, rs_off = 0, pix_off = 0, im_off = 0, tag_off = 0, mult_off = 0;
+    if (!dev) {
+        xyz_off = at, at += ext_align(12 * m);
+        rs_off = at, at += ext_align(8 * m);
+        if (src->pixel) pix_off = at, at += ext_align(4 * m);
+        if (src->intensity) im_off = at, at += ext_align(m);
+        if (s_tag) tag_off = at, at += ext_align(4 * m);
+        if (s_mult) mult_off = at, at += ext_align(4 * m);
+    }
+    int rc;
+    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, at))) return rc;
+    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256))) return rc;
+    const bool stage_out = delta && !delta->on_device;
+    const size_t ids_b = stage_out && ids_dst ? ext_align(4 * m) : 0;
+    if (stage_out && (ids_dst || upd_dst) && (rc = ext_grow_dev(&v.d_out, &v.out_bytes, ids_b + 4 * (size_t)std::min(v.M, R) + 4))) return rc;
+    if ((rc = vmap_grow(c, v.M + R))) return rc;
+    unsigned char* p = v.d_scratch;
+    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                           // {dropped, overflow}
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, updated, dropped, overflow, sum of m_r}
+    p += 512;
+    unsigned* d_where = reinterpret_cast<unsigned*>(p);
+    p += where_b;
+    unsigned* d_cnt_new = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_cnt_upd = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off_new = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned* d_off_upd = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum_new = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_new = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_bsum_upd = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_upd = reinterpret_cast<unsigned long long*>(p);
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
+
+    VimpSrc in{};
+    if (dev) {
+        in.xyz = src->xyz, in.rho_sigma = reinterpret_cast<const float2*>(src->rho_sigma), in.pixel = src->pixel;
+        in.intensity = src->intensity, in.tag = s_tag, in.multiplicity = s_mult;
+    } else {
+        unsigned char* b = v.d_scratch;
+        HIP_TRY(hipMemcpyAsync(b + xyz_off, src->xyz, 12 * m, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b + rs_off, src->rho_sigma, 8 * m, hipMemcpyHostToDevice, c->stream));
+        if (src->pixel) HIP_TRY(hipMemcpyAsync(b + pix_off, src->pixel, 4 * m, hipMemcpyHostToDevice, c->stream));
+        if (src->intensity) HIP_TRY(hipMemcpyAsync(b + im_off, src->intensity, m, hipMemcpyHostToDevice, c->stream));
+        if (s_tag) HIP_TRY(hipMemcpyAsync(b + tag_off, s_tag, 4 * m, hipMemcpyHostToDevice, c->stream));
+        if (s_mult) HIP_TRY(hipMemcpyAsync(b + mult_off, s_mult, 4 * m, hipMemcpyHostToDevice, c->stream));
+        in.xyz = reinterpret_cast<const float*>(b + xyz_off);
+        in.rho_sigma = reinterpret_cast<const float2*>(b + rs_off);
+        in.pixel = src->pixel ? reinterpret_cast<const unsigned*>(b + pix_off) : nullptr;
+        in.intensity = src->intensity ? b + im_off : nullptr;
+        in.tag = s_tag ? reinterpret_cast<const int*>(b + tag_off) : nullptr;
+        in.multiplicity = s_mult ? reinterpret_cast<const unsigned*>(b + mult_off) : nullptr;
+    }
+
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, 8, c->stream));
+    HIP_TRY(hipMemsetAsync(d_tot + 4, 0, 8, c->stream));
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long pblocks = (R + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vimp_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, in, R, b0 * BLOCK,
+                           v.inv, v.tb, d_where, d_ctr, d_tot + 4);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where, R,
+                           t0, d_cnt_new, d_cnt_upd);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_new, vt, d_off_new, d_bsum_new);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_new, (int)vb, d_boff_new);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_upd, vt, d_off_upd, d_bsum_upd);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_upd, (int)vb, d_boff_upd);
+    hipLaunchKernelGGL(k_vmap_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_new, d_boff_new, d_off_upd, d_boff_upd, d_ctr,
+                       d_tot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: created and updated
+    if (h_tot[3]) return fail(SDM_EHIP, "voxel map table overflow");
+    const long long created = (long long)h_tot[0], updated = (long long)h_tot[1], dropped = (long long)h_tot[2];
+    const long long stored = (long long)h_tot[4];
+
+    unsigned* d_ids = !ids_dst ? nullptr : stage_out ? reinterpret_cast<unsigned*>(v.d_out) : ids_dst;
+    unsigned* d_upd = !upd_dst ? nullptr : stage_out ? reinterpret_cast<unsigned*>(v.d_out + ids_b) : upd_dst;
+    const unsigned first_created = (unsigned)v.M, epoch = (unsigned)(v.calls + 1);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_ids, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
+                           first_created, R, t0, d_off_new, d_boff_new);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vimp_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
+                           first_created, R, t0, d_off_upd, d_boff_upd, d_upd);
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vimp_write, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
+                           first_created, epoch, R, b0 * BLOCK, in, d_ids);
+    HIP_TRY(hipGetLastError());
+    if (stage_out && ids_dst) HIP_TRY(hipMemcpyAsync(ids_dst, d_ids, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    if (stage_out && upd_dst && updated)
+        HIP_TRY(hipMemcpyAsync(upd_dst, d_upd, 4 * (size_t)updated, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    v.M += created;
+    v.points += stored;
+    v.dropped += dropped;
+    v.calls++;
+    if (delta) delta->created = created, delta->updated = updated, delta->dropped = dropped;
+    return SDM_OK;
+}
+
+int sdm_vmap_import_observations(sdm_ctx* c, long long count, sdm_vmap_obs_import* io)
+{
+    if (io) io->total = io->rejected = io->first_created = io->created = 0;
+    if (!c || !io) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (count < 0) return fail(SDM_EINVAL, "negative count");
+    if (io->map_count < 0) return fail(SDM_EINVAL, "negative map_count");
+    if (count > 0 && (!io->entry || !io->tag)) return fail(SDM_EINVAL, "null source (entry and tag are required)");
+    const bool dev = io->on_device != 0;
+    if (dev && ((uintptr_t)io->entry | (uintptr_t)io->tag | (uintptr_t)io->entry_map) % 4)
+        return fail(SDM_EINVAL, "device buffer not aligned (entry, tag, entry_map: 4 B)");
+    const long long P = count;
+    io->total = P;
+    io->first_created = o.E;
+    if (o.E + P > (1ll << 30))
+        return fail(SDM_EINVAL, "more than 2^30 observations and pairs: the observation set would exceed 2^31 slots");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (P == 0) {
+        o.calls++;
+        return SDM_OK;
+    }
+
+    // scratch, the staging of host sources, pinned mirror and growth: everything is allocated before anything is inserted
+    const size_t m = (size_t)P, mm = io->entry_map ? (size_t)io->map_count : 0;
+    const long long vt = (P + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t where_b = ext_align(4 * m), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1)),
+                 blk_b = ext_align(8 * (size_t)vb);
+    size_t at = 512 + where_b + tcnt_b + toff_b + 2 * blk_b;
+    const size_t ent_off = at, tag_off = ent_off + ext_align(4 * m), map_off = tag_off + ext_align(4 * m);
+    if (!dev) at = map_off + ext_align(4 * mm);
+    int rc;
+    if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, at))) return rc;
+    if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
+    // the tags a list may now hold bound its length (sdm_vmap_fetch_cameras' scan): device tags are read back for that, into
+    // a buffer made here, before anything is inserted
+    std::vector<int> back;
+    if (dev) {
+        try {
+            back.resize(m);
+        } catch (const std::bad_alloc&) {
+            return fail(SDM_EHIP, "host allocation of " + std::to_string(4 * m) + " B for the tags failed");
+        }
+    }
+    if ((rc = vobs_grow(c, o.E + P))) return rc;
+    unsigned char* p = o.d_scratch;
+    unsigned long long* d_ctr = reinterpret_cast<unsigned long long*>(p + 64);   // {rejected, stored or found, overflow}
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, rejected, stored or found, overflow}
+    p += 512;
+    unsigned* d_where = reinterpret_cast<unsigned*>(p);
+    p += where_b;
+    unsigned* d_cnt = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
+    const unsigned* d_entry = io->entry;
+    const int* d_tag = io->tag;
+    const unsigned* d_map = io->entry_map;
+    if (!dev) {
+        unsigned char* b = o.d_scratch;
+        HIP_TRY(hipMemcpyAsync(b + ent_off, io->entry, 4 * m, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b + tag_off, io->tag, 4 * m, hipMemcpyHostToDevice, c->stream));
+        if (mm) HIP_TRY(hipMemcpyAsync(b + map_off, io->entry_map, 4 * mm, hipMemcpyHostToDevice, c->stream));
+        d_entry = reinterpret_cast<const unsigned*>(b + ent_off);
+        d_tag = reinterpret_cast<const int*>(b + tag_off);
+        if (d_map) d_map = reinterpret_cast<const unsigned*>(b + map_off);  // (map_count == 0: never read)
+    }
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, 24, c->stream));
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long pblocks = (P + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, d_entry,
+                           d_tag, d_map, io->map_count, P, b0 * BLOCK, (unsigned)v.M, o.tb, d_where, d_ctr);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_where, P, t0,
+                           d_cnt);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt, vt, d_off, d_bsum);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)vb, d_boff);
+    hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off, d_boff, d_ctr, d_tot);
+    HIP_TRY(hipGetLastError());
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(o.h_pin);
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, c->stream));
+    const int* h_tag = io->tag;
+    if (dev) {
+        HIP_TRY(hipMemcpyAsync(back.data(), d_tag, 4 * m, hipMemcpyDeviceToHost, c->stream));
+        h_tag = back.data();
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: created
+    if (h_tot[3]) return fail(SDM_EHIP, "observation set overflow");
+    const long long created = (long long)h_tot[0];
+
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log, o.last_obs,
+                           o.ncam, d_where, (unsigned)o.E, P, t0, d_off, d_boff);
+    HIP_TRY(hipGetLastError());
+    // every tag >= 0 of the call counts, a rejected pair's too (its entry is not resolved here): `seen` is an upper bound of
+    // the tags the lists hold, which is all sdm_vmap_fetch_cameras' refusal needs, and the header says so
+    int last = -1;
+    for (size_t k = 0; k < m; k++) {  // (on the host, beside the commit; one binary search per change of tag)
+        const int t = h_tag[k];
+        if (t < 0 || t == last) continue;
+        last = t;
+        const auto it = std::lower_bound(o.seen.begin(), o.seen.end(), t);
+        if (it == o.seen.end() || *it != t) o.seen.insert(it, t);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    io->rejected = (long long)h_tot[1];
+    io->created = created;
+    o.E += created;
+    o.calls++;
     return SDM_OK;
 }
 

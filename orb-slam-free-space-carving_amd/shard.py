@@ -523,3 +523,78 @@ def pipeline_step(eng, pool, pl, min_d, max_d, exchange="allgather", group=None,
                 _gather_cache[key] = allgather_depth(pool, pl, group, _gather_cache.get(key))
                 eng.mark_depth_present([s for _, s in fetch_list(pl)])
         eng.inter_check_pointset(own, nbrs, commit=False)
+
+
+# ---- the persistent voxel map across ranks ------------------------------------------------------------------------------
+_VMAP_WIRE = (("xyz", "float32", 3), ("rho_sigma", "float32", 2), ("pixel", "uint32", 1), ("tag", "int32", 1),
+              ("multiplicity", "uint32", 1), ("intensity", "uint8", 1))
+
+
+def _vmap_pack(rec, log):
+    """one uint8 array: the record fields of _VMAP_WIRE, each padded to 4 bytes, then the log's entry and tag"""
+    import numpy as np
+    parts = []
+    for f, dt, _ in _VMAP_WIRE:
+        b = np.ascontiguousarray(rec[f], dtype=dt).reshape(-1).view(np.uint8)
+        parts += [b, np.zeros(-len(b) % 4, np.uint8)]
+    parts += [np.ascontiguousarray(log["entry"], dtype=np.uint32).view(np.uint8),
+              np.ascontiguousarray(log["tag"], dtype=np.int32).view(np.uint8)]
+    return np.concatenate(parts)
+
+
+def _vmap_unpack(buf, M, E):
+    import numpy as np
+    rec, at = {}, 0
+    for f, dt, per in _VMAP_WIRE:
+        n = M * per * np.dtype(dt).itemsize
+        a = buf[at:at + n].copy().view(dt)
+        rec[f] = a.reshape(M, per) if per > 1 else a
+        at += n + (-n % 4)
+    entry = buf[at:at + 4 * E].copy().view(np.uint32)
+    tag = buf[at + 4 * E:at + 8 * E].copy().view(np.int32)
+    return rec, entry, tag
+
+
+def vmap_allgather_merge(eng, group=None):
+    """Merges the persistent voxel maps (and observation logs) of all ranks of `group` into every rank's map.
+
+    Every rank fetches its whole map (vmap_fetch: every field but epoch) and its whole log (vmap_fetch_observations); the
+    ranks exchange the sizes (M, E) and then the payloads over the torch process group -- through host tensors (moved to
+    the device only for a backend that needs it), not through the engine's RCCL communicator.  Each rank then imports the
+    OTHER ranks' maps in rank order after its own: vmap_import of the records, then vmap_import_observations of the log
+    with the import's dst_ids as entry_map.  Rank r's result is therefore its own map followed by the others in rank
+    order; rank 0's is the canonical one and equals the map and camera lists of one engine that integrated and observed
+    every rank's keyframes in rank order (ids included, epoch apart).  On the other ranks the entries are the same set
+    with other ids.  Every map must have been opened with the same voxel_size.  Evidence counters and published flags do
+    not travel: carve and classify after the merge.
+
+    With no process group or world == 1 it does nothing and returns [].  Otherwise returns, per imported rank in rank
+    order, {"rank", "records": vmap_import's delta (with dst_ids), "observations": vmap_import_observations' outs}."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return []
+    import numpy as np
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    dev = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+    fields = tuple(f for f, _, _ in _VMAP_WIRE)
+    rec = eng.vmap_fetch(fields=fields)
+    log = eng.vmap_fetch_observations()
+    M, E = len(rec["pixel"]), len(log["entry"])
+    sizes = [torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(world)]
+    dist.all_gather(sizes, torch.tensor([M, E], dtype=torch.int64, device=dev), group=group)
+    sizes = [tuple(int(v) for v in s.cpu()) for s in sizes]
+    mine = _vmap_pack(rec, log)
+    longest = max(sum(m * per * np.dtype(dt).itemsize + (-(m * per * np.dtype(dt).itemsize) % 4) for _, dt, per in _VMAP_WIRE) + 8 * e
+                  for m, e in sizes)
+    send = torch.zeros(max(longest, 1), dtype=torch.uint8)
+    send[:len(mine)] = torch.from_numpy(mine)
+    recv = [torch.zeros(max(longest, 1), dtype=torch.uint8, device=dev) for _ in range(world)]
+    dist.all_gather(recv, send.to(dev), group=group)
+    out = []
+    for r in range(world):
+        if r == rank:
+            continue
+        records, entry, tag = _vmap_unpack(recv[r].cpu().numpy(), *sizes[r])
+        d = eng.vmap_import(records, dst_ids=True, updated=False)
+        o = eng.vmap_import_observations(entry, tag, entry_map=d["dst_ids"])
+        out.append({"rank": r, "records": d, "observations": o})
+    return out
