@@ -533,7 +533,8 @@ int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, in
  * Limits: a keyframe's contribution cannot be removed; stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
  * integrate the resident slots again); free-space evidence is kept per entry by sdm_vmap_carve and the camera
  * lists by sdm_vmap_observe (both below); one rank only per map: the maps of several ranks, a saved map or a map of
- * another voxel_size come in through sdm_vmap_import (below). */
+ * another voxel_size come in through sdm_vmap_import (below).  Under adjusted poses sdm_vmap_repose (below) re-places
+ * the stored points without the slots. */
 typedef struct {
     long long voxels;       /* M */
     long long points;       /* mergeable points integrated */
@@ -608,7 +609,8 @@ int sdm_vmap_fetch(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long l
  * Limits: evidence is relative to the entries present at each carve, so -- unlike the map itself -- it is NOT invariant
  * under re-splitting integrates and carves against each other; carving the same slots twice counts twice; the counters go
  * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed; one rank only: the
- * counters do not travel with sdm_vmap_import (below) -- carve on the merged map. */
+ * counters do not travel with sdm_vmap_import (below) -- carve on the merged map.  sdm_vmap_repose (below) carries or
+ * restarts the counters when the poses move. */
 typedef struct {
     int end_margin;            /* in: >= 0 */
     int max_steps;             /* in: 1 .. SDM_FREESPACE_MAX_STEPS */
@@ -706,7 +708,8 @@ int sdm_vmap_fetch_evidence(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*
  * capacity); the lists go stale with sdm_set_pose exactly as the stored xyz do (remedy: sdm_vmap_clear, integrate and
  * observe the resident slots again); an observation cannot be removed: removing one and shrinking the camera lists on
  * the persistent map remain later work; one rank only per log: the logs of several ranks merge through
- * sdm_vmap_import_observations (below). */
+ * sdm_vmap_import_observations (below).  sdm_vmap_repose (below) carries the log through its id map when the poses
+ * move. */
 typedef struct {
     long long plain_total;     /* out: T */
     long long unmapped;        /* out: plain points without an entry */
@@ -799,7 +802,8 @@ int sdm_vmap_fetch_cameras(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/
  * Limits: the pass is O(M) per call on the device; there is no hysteresis -- an entry whose evidence hovers at a threshold
  * is accepted and retracted again and again, and damping that is the consumer's; the flags go stale with sdm_set_pose
  * exactly as the evidence does (remedy: sdm_vmap_clear, then integrate, observe, carve and classify the resident slots
- * again); one rank only: the flags do not travel with sdm_vmap_import (below) -- classify the merged map. */
+ * again); one rank only: the flags do not travel with sdm_vmap_import (below) -- classify the merged map.
+ * sdm_vmap_repose (below) carries or restarts the flags when the poses move. */
 typedef struct {
     unsigned min_multiplicity;
     unsigned min_cameras;
@@ -920,6 +924,75 @@ typedef struct {
     long long total, rejected, first_created, created;    /* out */
 } sdm_vmap_obs_import;
 int sdm_vmap_import_observations(sdm_ctx *ctx, long long count, sdm_vmap_obs_import *io);
+/* Re-placing the persistent map under new keyframe poses: bundle adjustment and loop closing move poses long after the
+ * slots of the keyframes that built the map were recycled, and the four limits above all end in "clear and integrate the
+ * resident slots again".  An entry's record holds what its xyz was computed from -- the winning point's pixel, its rho and
+ * the keyframe's tag -- so sdm_vmap_repose recomputes every entry's xyz on the device from a table of (tag, K, Tcw),
+ * bins the entries again and carries the observation log, the counters and the flags through the id map.  Nothing in
+ * the reference does this; the semantics are this library's (tests/vmap_repose_np.py restates them in NumPy).  Requires an
+ * open map.  tags[n_poses], K[n_poses][4] = {fx, fy, cx, cy} and Tcw[n_poses][12] are host arrays; K is passed because the
+ * slot of an old keyframe is long gone.
+ *   - New xyz of old entry i: if the record's tag equals tags[p], xyz becomes exactly what UpdateSemiDensePointSet's
+ *     arithmetic (sdm_pointset) gives for K[p], Tcw[p], x = pixel & 0xffff, y = pixel >> 16 and the record's rho -- the same
+ *     device function, no FMA, (double)rho < 1e-6 -> (0, 0, 0) included; the 2-pixel inset plays no part.  An entry whose
+ *     tag is not in the table keeps its xyz bits.  A non-finite pose is no error: it yields non-finite xyz.
+ *   - Re-binning: the result is defined as if the old entries i = 0 .. M-1 were imported by sdm_vmap_import, in increasing
+ *     i, into an empty map of the same voxel_size, record i carrying its new xyz, its pixel, rho_sigma, intensity and tag
+ *     and m_i = its multiplicity: a record whose new xyz is unmergeable is dropped; new ids are the order of first
+ *     appearance, so survivors keep their relative order; within a voxel the smallest key(sigma) wins and a tie goes to
+ *     the lower old id; multiplicities add and saturate at 2^32 - 1.  One difference: the surviving record keeps its OLD
+ *     epoch.  remap[i] is the entry that holds old entry i's voxel after the call, 0xFFFFFFFF for a dropped one.
+ *   - Map info: calls += 1 (the call takes a call number, though no epoch becomes it); voxels = the new M; points, dropped,
+ *     table_slots and rehashes are unchanged (the table never shrinks; the new M is at most the old).
+ *   - Observation log: rebuilt as if the old log, in log order, were passed to sdm_vmap_import_observations with
+ *     entry_map = remap into an empty log: pairs of dropped entries vanish, pairs that become equal collapse, the
+ *     survivors keep their relative order.  The set's slots, its rehashes and the obs info's calls are unchanged.  If no
+ *     observe or import of observations has stored a pair, nothing is allocated or touched.
+ *   - Evidence and published flags: with carry == 0 both counters and the flag are 0 for every new entry (they restart);
+ *     with carry == 1 a new entry's crossings and ends are the 64-bit sums over the old entries mapped to it and its flag
+ *     the OR of theirs.  The class info's `published` follows the flags; its calls is unchanged.
+ *   - n_poses == 0 (NULL arrays allowed) is the identity on the map, the ids, the camera lists and -- with carry == 1 --
+ *     evidence and flags: remap[i] = i.  Log indices may still be renumbered: the rebuilt log keeps the relative order
+ *     of the surviving pairs.
+ *   - Delta (sdm_vmap_repose_delta): examined = M before; reposed = entries whose tag is in the table; moved = of those,
+ *     entries whose xyz changed in at least one bit; dropped; voxels = M after; merged = examined - dropped - voxels;
+ *     observations_before and observations = E before and after.  remap follows delta->on_device.
+ * Everything is copied bits, integer reductions, or the one float formula per entry: every output is bitwise the same from
+ * run to run, whatever the table layout.
+ * Errors, all raised before anything changes (a refused call leaves all four infos, a full fetch, the log, the evidence
+ * and the flags as they were; no refusal depends on device data):
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: a NULL ctx or delta; n_poses < 0; a NULL tags, K or Tcw with n_poses > 0; a tag outside [0, 2^31); a tag
+ *     listed twice; carry not 0 or 1; a misaligned device remap; remap != NULL with remap_capacity < M (examined is filled).
+ *   SDM_EHIP: an allocation failure -- everything is allocated before anything is written.
+ * On an argument or state refusal the outs are 0, except examined once known.
+ * Changes no plane, flag, list or counter of the engine outside the map.
+ * Cost: the pose table (84 B per pose, sorted by tag on the host) is uploaded once; per old entry one binary search and
+ * 29 B read, 12 B of scratch xyz written; then one sdm_vmap_import of M device records into the emptied table (its cost
+ * above, without the staging), 4 B of remap and a 37 B record per new entry; with carry 17 B read per old entry and up to
+ * two 64-bit atomic adds and a byte; one pass over the new flags; one sdm_vmap_import_observations of the E old pairs
+ * through remap, in place.  Two memsets over the table and the set.  Two host waits: the counts, the end; 4 B per old
+ * entry cross the link for a host remap and nothing else does.  Measured: DESIGN.md s.22.
+ * Memory: the peak extra is one second set of records (37 B per record of capacity) plus 16 B per old entry of scratch
+ * (xyz, table position), 4 B more for a remap that is not a device buffer of the caller's, and with carry a second set
+ * of counters and flags (17 B per record of capacity); the old sets are freed before the call returns.  The log and the
+ * set are rebuilt in their own storage with 4 B per old pair of scratch.
+ * Limits: only each voxel's winning point is re-placed -- the points that lost are gone, so a reposed map is not the map
+ * of integrating everything again under the new poses; carried evidence belongs to rays walked under the old poses; two
+ * successive reposes are not one repose with the union table (entries merged by the first stay merged); ids and log
+ * indices change and remap is the consumer's only bridge; one rank only per map. */
+typedef struct {
+    unsigned *remap;              /* in: [remap_capacity] or NULL; out: new id of old entry i, 0xFFFFFFFF if dropped */
+    long long remap_capacity;     /* in: >= M before the call when remap != NULL */
+    int on_device;                /* in: 1: remap is device memory of this context's GPU (4-byte aligned) */
+    int carry;                    /* in: 0: evidence counters and published flags restart at 0; 1: carried (above) */
+    long long examined;           /* out: M before the call */
+    long long reposed, moved, dropped, merged;   /* out */
+    long long voxels;             /* out: M after the call */
+    long long observations_before, observations;   /* out: E before / after */
+} sdm_vmap_repose_delta;
+int sdm_vmap_repose(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses]*/, const float *K /*[n_poses][4]*/,
+                    const float *Tcw /*[n_poses][12]*/, sdm_vmap_repose_delta *delta);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

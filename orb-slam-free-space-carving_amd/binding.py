@@ -149,6 +149,14 @@ class VmapObsImport(C.Structure):
                 ("created", C.c_longlong)]
 
 
+class VmapReposeDelta(C.Structure):
+    """sdm_vmap_repose_delta"""
+    _fields_ = [("remap", C.c_void_p), ("remap_capacity", C.c_longlong), ("on_device", C.c_int), ("carry", C.c_int),
+                ("examined", C.c_longlong), ("reposed", C.c_longlong), ("moved", C.c_longlong), ("dropped", C.c_longlong),
+                ("merged", C.c_longlong), ("voxels", C.c_longlong), ("observations_before", C.c_longlong),
+                ("observations", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -177,6 +185,8 @@ VMAP_CLASS_OUTS = ("examined", "accepted", "retracted", "published_total")
 # the outs of sdm_vmap_import and sdm_vmap_import_observations
 VMAP_IMPORT_OUTS = ("total", "dropped", "first_created", "created", "updated")
 VMAP_OBS_IMPORT_OUTS = ("total", "rejected", "first_created", "created")
+# the outs of sdm_vmap_repose
+VMAP_REPOSE_OUTS = ("examined", "reposed", "moved", "dropped", "merged", "voxels", "observations_before", "observations")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -255,6 +265,7 @@ SYMBOLS = [
     ("sdm_vmap_import", C.c_int, [_ctx, C.POINTER(PointBuffers), C.POINTER(VmapFields), C.c_longlong,
                                   C.POINTER(VmapImportDelta)]),
     ("sdm_vmap_import_observations", C.c_int, [_ctx, C.c_longlong, C.POINTER(VmapObsImport)]),
+    ("sdm_vmap_repose", C.c_int, [_ctx, C.c_int, _ip, _f32p, _f32p, C.POINTER(VmapReposeDelta)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1429,6 +1440,46 @@ class Engine:
             e.total, e.first_created = int(io.total), int(io.first_created)
             raise e
         return {f: int(getattr(io, f)) for f in VMAP_OBS_IMPORT_OUTS}
+
+    def vmap_repose(self, tags, K, Tcw, carry=False, remap=True):
+        """Re-places the voxel map under new keyframe poses (sdm_vmap_repose).  tags int32[n], K float32[n, 4] = (fx, fy,
+        cx, cy) and Tcw float32[n, 12]: every entry whose record carries tags[p] gets the xyz of its stored pixel and rho
+        under K[p], Tcw[p]; the entries are binned again as vmap_import would bin them, the observation log follows, and
+        evidence counters and published flags restart at 0 (carry False) or are summed / ORed over the entries that merge
+        (carry True).  n = 0 (tags None or empty) re-places nothing.  Returns {"examined", "reposed", "moved", "dropped",
+        "merged", "voxels", "observations_before", "observations"} and "remap" (uint32[examined]: the new id of every old
+        entry, 0xFFFFFFFF for a dropped one).  remap: True -- a NumPy array is made here; False -- not returned; or the
+        destination, a uint32 array (pageable, or pinned from host_alloc) or a torch device tensor of 4-byte elements.  A
+        refusal raises SdmError with .examined."""
+        tg = np.ascontiguousarray(np.asarray([] if tags is None else tags, dtype=np.int32).reshape(-1))
+        n = len(tg)
+        tp = kp = pp = None
+        if n:
+            k4, kp = _f32(np.asarray(K, dtype=np.float32).reshape(-1, 4))
+            t12, pp = _f32(np.asarray(Tcw, dtype=np.float32).reshape(-1, 12))
+            if len(k4) != n or len(t12) != n:
+                raise ValueError("K and Tcw: need one row per tag")
+            tp = tg.ctypes.data_as(_ip)
+        d = VmapReposeDelta()
+        d.carry = int(carry)
+        dest = None
+        if remap is True:
+            dest = np.empty(max(self.vmap_info()["voxels"], 1), np.uint32)
+        elif remap is not False and remap is not None:
+            dest = remap
+        if dest is not None:
+            kinds = set()
+            d.remap, d.remap_capacity = self._dest("remap", dest, np.uint32, 1, kinds)
+            d.on_device = 1 if kinds == {"device"} else 0
+        rc = self.lib.sdm_vmap_repose(self.ctx, n, tp, kp, pp, C.byref(d))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            e.examined = int(d.examined)
+            raise e
+        res = {f: int(getattr(d, f)) for f in VMAP_REPOSE_OUTS}
+        if dest is not None:
+            res["remap"] = dest[:res["examined"]]
+        return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

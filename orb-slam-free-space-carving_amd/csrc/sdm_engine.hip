@@ -40,6 +40,7 @@
 #include "sdm_vmap_obs.h"
 #include "sdm_vmap_class.h"
 #include "sdm_vmap_import.h"
+#include "sdm_vmap_repose.h"
 
 using namespace sdm;
 
@@ -4207,7 +4208,7 @@ int sdm_vmap_import(sdm_ctx* c, const sdm_point_buffers* src, const sdm_vmap_fie
                            first_created, R, t0, d_off_upd, d_boff_upd, d_upd);
     for (long long b0 = 0; b0 < pblocks; b0 += per)
         hipLaunchKernelGGL(k_vimp_write, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
-                           first_created, epoch, R, b0 * BLOCK, in, d_ids);
+                           first_created, epoch, R, b0 * BLOCK, in, d_ids, (const unsigned*)nullptr);
     HIP_TRY(hipGetLastError());
     if (stage_out && ids_dst) HIP_TRY(hipMemcpyAsync(ids_dst, d_ids, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (stage_out && upd_dst && updated)
@@ -4336,6 +4337,257 @@ int sdm_vmap_import_observations(sdm_ctx* c, long long count, sdm_vmap_obs_impor
     io->created = created;
     o.E += created;
     o.calls++;
+    return SDM_OK;
+}
+
+// ---- re-placing the persistent voxel map under new poses (sdm_vmap_repose.h) ----------------------------------------------
+namespace {
+// device blocks made for a repose; whatever is still held when the call leaves is freed (after the swap: the old ones)
+struct VrepBlocks {
+    unsigned char *rec = nullptr, *evid = nullptr, *pub = nullptr;
+    ~VrepBlocks()
+    {
+        (void)hipFree(rec);
+        (void)hipFree(evid);
+        (void)hipFree(pub);
+    }
+};
+}  // namespace
+
+int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, const float* Tcw, sdm_vmap_repose_delta* delta)
+{
+    if (delta)
+        delta->examined = delta->reposed = delta->moved = delta->dropped = delta->merged = delta->voxels =
+            delta->observations_before = delta->observations = 0;
+    if (!c || !delta) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (n_poses < 0) return fail(SDM_EINVAL, "negative n_poses");
+    if (n_poses > 0 && (!tags || !K || !Tcw)) return fail(SDM_EINVAL, "null pose table (tags, K and Tcw are required)");
+    if (delta->carry != 0 && delta->carry != 1) return fail(SDM_EINVAL, "carry must be 0 or 1");
+    const size_t np = (size_t)n_poses;
+    std::vector<int> order;  // the table's rows by ascending tag
+    try {
+        order.resize(np);
+    } catch (const std::bad_alloc&) {
+        return fail(SDM_EHIP, "host allocation for the pose table failed");
+    }
+    for (size_t p = 0; p < np; p++) {
+        if (tags[p] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
+        order[p] = (int)p;
+    }
+    std::sort(order.begin(), order.end(), [tags](int a, int b) { return tags[a] < tags[b]; });
+    for (size_t p = 1; p < np; p++)
+        if (tags[order[p]] == tags[order[p - 1]]) return fail(SDM_EINVAL, "tag " + std::to_string(tags[order[p]]) + " listed twice");
+    unsigned* remap_dst = delta->remap;
+    const bool remap_dev = remap_dst && delta->on_device;
+    if (remap_dev && (uintptr_t)remap_dst % 4) return fail(SDM_EINVAL, "device buffer not aligned (remap: 4 B)");
+    const long long M = v.M, E = o.E;
+    delta->examined = M;
+    if (remap_dst && delta->remap_capacity < M)
+        return fail(SDM_EINVAL, "remap_capacity " + std::to_string(delta->remap_capacity) + " < entries = " + std::to_string(M) +
+                                    " (examined filled)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    delta->observations_before = delta->observations = E;
+    if (M == 0) {  // (no entry: no pair, no counter, no flag)
+        v.calls++;
+        return SDM_OK;
+    }
+
+    // scratch, pose table, the second set of records (with carry: of counters and flags), the log's scratch: everything is
+    // allocated before anything is written
+    const bool carry = delta->carry == 1;
+    const size_t m = (size_t)M;
+    const long long vt = (M + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t where_b = ext_align(4 * m), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
+    const size_t blk_b = ext_align(8 * (size_t)vb);
+    size_t at = 512 + where_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b;
+    const size_t xyz_off = at;
+    at += ext_align(12 * m);
+    const size_t tags_b = ext_align(4 * np), poses_b = ext_align(sizeof(KfMeta) * np);
+    const size_t tab_off = at;
+    at += tags_b + poses_b;
+    const size_t remap_off = at;
+    if (!remap_dev) at += ext_align(4 * m);
+    int rc;
+    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, at))) return rc;
+    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tags_b + poses_b))) return rc;
+    const long long ot = (E + EXT_TILE - 1) / EXT_TILE;
+    const long long ob = (ot + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t owhere_b = ext_align(4 * (size_t)E), otcnt_b = ext_align(4 * (size_t)ot), otoff_b = ext_align(4 * (size_t)(ot + 1)),
+                 oblk_b = ext_align(8 * (size_t)ob);
+    if (E > 0) {
+        if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, 512 + owhere_b + otcnt_b + otoff_b + 2 * oblk_b))) return rc;
+        if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
+    }
+    VrepBlocks nb;
+    VmapRecords nr{};
+    if ((rc = vmap_make_records(v.rec_cap, &nb.rec, &nr))) return rc;
+    unsigned long long *ncr = nullptr, *nen = nullptr;
+    if (carry && v.d_evid && (rc = vmap_make_evidence(c, v.rec_cap, &nb.evid, &ncr, &nen))) return rc;
+    if (carry && v.cls.d_pub && (rc = vmap_make_published(c, v.rec_cap, &nb.pub))) return rc;
+
+    unsigned char* p = v.d_scratch;
+    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                            // {dropped, overflow}
+    unsigned long long* d_rep = reinterpret_cast<unsigned long long*>(p + 64);   // {reposed, moved, published}
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, updated, dropped, overflow, sum of m_i}
+    p += 512;
+    unsigned* d_where = reinterpret_cast<unsigned*>(p);
+    p += where_b;
+    unsigned* d_cnt_new = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_cnt_upd = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off_new = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned* d_off_upd = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum_new = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_new = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_bsum_upd = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_upd = reinterpret_cast<unsigned long long*>(p);
+    float* d_xyz = reinterpret_cast<float*>(v.d_scratch + xyz_off);
+    int* d_tags = reinterpret_cast<int*>(v.d_scratch + tab_off);
+    KfMeta* d_poses = reinterpret_cast<KfMeta*>(v.d_scratch + tab_off + tags_b);
+    unsigned* d_remap = remap_dev ? remap_dst : reinterpret_cast<unsigned*>(v.d_scratch + remap_off);
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);  // [0..5) the import's totals, [8..11) d_rep
+    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
+    KfMeta* h_poses = reinterpret_cast<KfMeta*>(v.h_pin + 256 + tags_b);
+    for (size_t q = 0; q < np; q++) {
+        const size_t s = (size_t)order[q];
+        h_tags[q] = tags[s];
+        std::memset(&h_poses[q], 0, sizeof(KfMeta));
+        fill_meta(h_poses[q], K + 4 * s, Tcw + 12 * s);
+    }
+
+    // the new xyz of every old entry
+    HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 512, c->stream));
+    if (np) HIP_TRY(hipMemcpyAsync(d_tags, h_tags, tags_b + poses_b, hipMemcpyHostToDevice, c->stream));
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long pblocks = (M + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vrep_project, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.rec, M,
+                           b0 * BLOCK, d_tags, d_poses, n_poses, d_xyz, d_rep);
+    // one import of the old records, at their new xyz, into the emptied table and the second set of records
+    HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
+    HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
+    VimpSrc in{};
+    in.xyz = d_xyz, in.rho_sigma = v.rec.rho_sigma, in.pixel = v.rec.pixel;
+    in.intensity = v.rec.intensity, in.tag = v.rec.tag, in.multiplicity = v.rec.multiplicity;
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vimp_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, in, M, b0 * BLOCK,
+                           v.inv, v.tb, d_where, d_ctr, d_tot + 4);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where, M, t0,
+                           d_cnt_new, d_cnt_upd);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_new, vt, d_off_new, d_bsum_new);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_new, (int)vb, d_boff_new);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_upd, vt, d_off_upd, d_bsum_upd);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_upd, (int)vb, d_boff_upd);
+    hipLaunchKernelGGL(k_vmap_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_new, d_boff_new, d_off_upd, d_boff_upd, d_ctr,
+                       d_tot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: the new M
+    if (h_tot[3]) return fail(SDM_EHIP, "voxel map table overflow");
+    const long long M2 = (long long)h_tot[0], dropped = (long long)h_tot[2];
+
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vmap_ids, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where, 0u, M,
+                           t0, d_off_new, d_boff_new);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vimp_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where, 0u,
+                           M, t0, d_off_upd, d_boff_upd, (unsigned*)nullptr);
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vimp_write, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where,
+                           0u, 0u, M, b0 * BLOCK, in, d_remap, (const unsigned*)v.rec.epoch);
+    // counters and flags: carried through remap into the second set, or back to 0 where they are
+    const size_t evid_b = 2 * ext_align(8 * (size_t)v.rec_cap);
+    if (carry && (nb.evid || nb.pub)) {
+        for (long long b0 = 0; b0 < pblocks; b0 += per)
+            hipLaunchKernelGGL(k_vrep_carry, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, d_remap, M,
+                               b0 * BLOCK, nb.evid ? v.crossings : nullptr, nb.evid ? v.ends : nullptr, ncr, nen,
+                               nb.pub ? v.cls.d_pub : nullptr, nb.pub);
+        if (nb.pub) {
+            const long long cblocks = (M2 + BLOCK - 1) / BLOCK;
+            for (long long b0 = 0; b0 < cblocks; b0 += per)
+                hipLaunchKernelGGL(k_vrep_count, dim3((unsigned)std::min(per, cblocks - b0)), dim3(BLOCK), 0, c->stream, nb.pub, M2,
+                                   b0 * BLOCK, d_rep + 2);
+        }
+    } else if (!carry) {
+        if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, evid_b, c->stream));
+        if (v.cls.d_pub) HIP_TRY(hipMemsetAsync(v.cls.d_pub, 0, (size_t)v.rec_cap, c->stream));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot + 8, d_rep, 24, hipMemcpyDeviceToHost, c->stream));
+    if (remap_dst && !remap_dev) HIP_TRY(hipMemcpyAsync(remap_dst, d_remap, 4 * m, hipMemcpyDeviceToHost, c->stream));
+
+    // the log: the old pairs, in log order, through remap into the emptied set, in place
+    unsigned long long* h_otot = nullptr;
+    if (E > 0) {
+        unsigned char* q = o.d_scratch;
+        unsigned long long* d_octr = reinterpret_cast<unsigned long long*>(q + 64);   // {rejected, stored or found, overflow}
+        unsigned long long* d_otot = reinterpret_cast<unsigned long long*>(q + 256);  // {created, rejected, stored or found, overflow}
+        q += 512;
+        unsigned* d_owhere = reinterpret_cast<unsigned*>(q);
+        q += owhere_b;
+        unsigned* d_ocnt = reinterpret_cast<unsigned*>(q);
+        q += otcnt_b;
+        unsigned* d_ooff = reinterpret_cast<unsigned*>(q);
+        q += otoff_b;
+        unsigned long long* d_obsum = reinterpret_cast<unsigned long long*>(q);
+        q += oblk_b;
+        unsigned long long* d_oboff = reinterpret_cast<unsigned long long*>(q);
+        const size_t b4 = ext_align(4 * (size_t)v.rec_cap);
+        HIP_TRY(hipMemsetAsync(o.d_table, 0xff, 20 * (size_t)o.cap, c->stream));
+        HIP_TRY(hipMemsetAsync(o.d_ent, 0xff, b4, c->stream));
+        HIP_TRY(hipMemsetAsync(o.d_ent + b4, 0, b4, c->stream));
+        HIP_TRY(hipMemsetAsync(d_octr, 0, 24, c->stream));
+        const long long eblocks = (E + BLOCK - 1) / BLOCK;
+        for (long long b0 = 0; b0 < eblocks; b0 += per)
+            hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
+                               (const unsigned*)o.log.entry, (const int*)o.log.tag, (const unsigned*)d_remap, M, E, b0 * BLOCK,
+                               (unsigned)M2, o.tb, d_owhere, d_octr);
+        for (long long t0 = 0; t0 < ot; t0 += per)
+            hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_owhere, E, t0,
+                               d_ocnt);
+        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_ocnt, ot, d_ooff, d_obsum);
+        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_obsum, (int)ob, d_oboff);
+        hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, ot, d_ooff, d_oboff, d_octr, d_otot);
+        for (long long t0 = 0; t0 < ot; t0 += per)
+            hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log,
+                               o.last_obs, o.ncam, d_owhere, 0u, E, t0, d_ooff, d_oboff);
+        HIP_TRY(hipGetLastError());
+        h_otot = reinterpret_cast<unsigned long long*>(o.h_pin);
+        HIP_TRY(hipMemcpyAsync(h_otot, d_otot, 32, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end
+    if (h_otot && h_otot[3]) return fail(SDM_EHIP, "observation set overflow");
+
+    // the second sets become the map's; the old ones go with `nb`
+    std::swap(v.d_rec, nb.rec);
+    v.rec = nr;
+    if (nb.evid) {
+        std::swap(v.d_evid, nb.evid);
+        v.crossings = ncr;
+        v.ends = nen;
+    }
+    if (nb.pub) std::swap(v.cls.d_pub, nb.pub);
+    v.cls.published = carry ? (long long)h_tot[10] : 0;
+    v.M = M2;
+    v.calls++;
+    if (h_otot) o.E = (long long)h_otot[0];
+    delta->reposed = (long long)h_tot[8];
+    delta->moved = (long long)h_tot[9];
+    delta->dropped = dropped;
+    delta->voxels = M2;
+    delta->merged = M - dropped - M2;
+    delta->observations = o.E;
     return SDM_OK;
 }
 

@@ -150,10 +150,12 @@ __global__ __launch_bounds__(BLOCK) void k_vimp_commit(VmapTable tb, VmapRecords
 
 // one lane per source record r0 + thread (a later launch than k_vimp_commit): every record learns its entry; the call's
 // winner of a new or beaten voxel -- the one lane that touches record id -- writes the record from the sources and puts
-// cval back to its identity
+// cval back to its identity.  src_epoch (sdm_vmap_repose: the records move, their history stays) replaces the call's epoch
+// by the source record's
 __global__ __launch_bounds__(BLOCK) void k_vimp_write(VmapTable tb, VmapRecords rec, const unsigned* __restrict__ where,
                                                       unsigned first_created, unsigned epoch, long long R, long long r0,
-                                                      VimpSrc src, unsigned* __restrict__ dst_ids)
+                                                      VimpSrc src, unsigned* __restrict__ dst_ids,
+                                                      const unsigned* __restrict__ src_epoch)
 {
     const long long r = r0 + (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (r >= R) return;
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(BLOCK) void k_vimp_write(VmapTable tb, VmapRecords 
     rec.rho_sigma[e] = src.rho_sigma[r];
     rec.intensity[e] = src.intensity ? src.intensity[r] : (unsigned char)0;
     rec.tag[e] = src.tag ? src.tag[r] : 0;
-    rec.epoch[e] = epoch;
+    rec.epoch[e] = src_epoch ? src_epoch[r] : epoch;
 }
 
 // pairs k0 + thread; ctr = {rejected pairs, stored or found pairs, overflow} (k_vobs_totals' layout)
