@@ -530,7 +530,7 @@ int sdm_extract_points_voxel_freespace(sdm_ctx *ctx, int n, const int *slots, in
  * the records grow geometrically by device copies.  Memory: 28 B per table slot, 37 B per record.  Three host waits: T,
  * the counts, the end.  sdm_vmap_fetch: one copy per field of exactly count elements (range form), after one gather
  * launch (ids form).
- * Limits: a keyframe's contribution cannot be removed; stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
+ * Limits: a keyframe's contribution cannot be removed by these calls (sdm_vmap_retire, below, removes it); stored xyz go stale after sdm_set_pose (remedy: sdm_vmap_clear and
  * integrate the resident slots again); free-space evidence is kept per entry by sdm_vmap_carve and the camera
  * lists by sdm_vmap_observe (both below); one rank only per map: the maps of several ranks, a saved map or a map of
  * another voxel_size come in through sdm_vmap_import (below).  Under adjusted poses sdm_vmap_repose (below) re-places
@@ -608,7 +608,8 @@ int sdm_vmap_fetch(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long l
  * Memory: 16 B per record of capacity, allocated at the first carve.  Two host waits: T, the end (with the totals).
  * Limits: evidence is relative to the entries present at each carve, so -- unlike the map itself -- it is NOT invariant
  * under re-splitting integrates and carves against each other; carving the same slots twice counts twice; the counters go
- * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed; one rank only: the
+ * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed from the counters
+ * (sdm_vmap_retire, below, removes its entries and pairs, and its carry = 1 keeps the rays it added); one rank only: the
  * counters do not travel with sdm_vmap_import (below) -- carve on the merged map.  sdm_vmap_repose (below) carries or
  * restarts the counters when the poses move. */
 typedef struct {
@@ -709,7 +710,8 @@ int sdm_vmap_fetch_evidence(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*
  * observe the resident slots again); an observation cannot be removed: removing one and shrinking the camera lists on
  * the persistent map remain later work; one rank only per log: the logs of several ranks merge through
  * sdm_vmap_import_observations (below).  sdm_vmap_repose (below) carries the log through its id map when the poses
- * move. */
+ * move.  sdm_vmap_retire (below) is that later work: it removes the observations of a set of keyframes and shortens the
+ * camera lists. */
 typedef struct {
     long long plain_total;     /* out: T */
     long long unmapped;        /* out: plain points without an entry */
@@ -904,7 +906,8 @@ int sdm_vmap_fetch_published(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL
  * Limits: evidence counters and published flags do not travel: sdm_vmap_carve and sdm_vmap_classify run on the merged
  * map, and evidence carved on one rank is relative to that rank's entries, so it does not add up across ranks; the
  * records of several ranks reach one context through host or device buffers the caller moves -- there is no collective
- * inside the call; a record cannot be removed. */
+ * inside the call; a record cannot be removed by an import (sdm_vmap_retire, below, removes the records of retired
+ * keyframes). */
 typedef struct {
     unsigned *dst_ids;            /* in: [count] or NULL; out: entry id of record r, 0xFFFFFFFF for a dropped one */
     unsigned *updated_ids;        /* in: [updated_capacity] or NULL */
@@ -993,6 +996,90 @@ typedef struct {
 } sdm_vmap_repose_delta;
 int sdm_vmap_repose(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses]*/, const float *K /*[n_poses][4]*/,
                     const float *Tcw /*[n_poses][12]*/, sdm_vmap_repose_delta *delta);
+/* Retiring keyframes from the persistent map: ORB-SLAM culls keyframes all the time, the reference skips the semi-dense
+ * points of a bad keyframe, and its transcript has "del observation" next to "del point".  sdm_vmap_retire removes a set R
+ * of keyframe tags from the map on the device and reports exactly what a consumer has to delete.  The semantics are this
+ * library's (tests/vmap_retire_np.py restates them in NumPy).  Requires an open map.  tags[n_tags] is a host array; the old
+ * entries are i = 0 .. M-1 and the old log pairs k = 0 .. E-1.
+ *   - Pairs: a pair (entry, tag) is retired iff tag is in R.
+ *   - Survivors.  mode SDM_VMAP_RETIRE_WINNER: entry i survives iff its record's tag is not in R (the reference's
+ *     behaviour: the points of a bad keyframe disappear).  mode SDM_VMAP_RETIRE_UNOBSERVED: entry i survives iff at least
+ *     one of its pairs is not retired -- a voxel lives as long as a live keyframe saw it.  This mode presupposes the recipe
+ *     "integrate, then observe" per block: an entry that was never observed does not survive, and with E == 0 the map
+ *     empties.  orphaned counts the survivors whose record's tag is in R (possible in mode UNOBSERVED only); their record
+ *     stays bit for bit, retired tag included, because the points that lost are gone.
+ *   - Map: new id = rank of i among the survivors, so survivors keep their relative order; every field of a survivor's
+ *     record (xyz, pixel, rho_sigma, intensity, tag, multiplicity, epoch) is copied bits.  remap[i] is the new id, or
+ *     0xFFFFFFFF for a dropped entry.  Map info: calls += 1; voxels = the new M; points, dropped, table_slots and rehashes
+ *     are unchanged (the table never shrinks).  After the call exactly the survivors' voxels are found, under their new ids.
+ *   - Log: the new log is the old log, in log order, without the retired pairs and without the pairs of dropped entries,
+ *     entry ids through remap.  Nothing collapses (survivors are distinct).  Chains, list lengths, the set and
+ *     sdm_vmap_fetch_cameras follow; the obs info's calls, slots and rehashes are unchanged.  removed counts the retired
+ *     pairs on SURVIVING entries, listed with OLD entry ids in old log order; the pairs that vanish with a dropped entry are
+ *     observations_before - observations - removed and are not listed ("del point" covers them).  If no pair was ever
+ *     stored, nothing of the log is allocated or touched.
+ *   - Evidence and published flags: with carry == 1 a survivor keeps its two counters and its flag; with carry == 0 all
+ *     restart at 0.  The class info's `published` follows; its calls is unchanged.
+ *   - Lists for the consumer: dropped_ids holds OLD ids, ascending, and dropped_published their flag before the call -- emit
+ *     "del point" for those with flag 1; removed_entry / removed_tag are for "del observation"; then apply remap.
+ *     dropped_published needs dropped_ids and removed_tag needs removed_entry (they share the capacity).
+ *   - commit == 0: every out and every list is computed and nothing in the context changes (as sdm_vmap_classify).
+ *   - n_tags == 0 (NULL tags allowed) is the identity in mode WINNER: remap[i] = i; with carry == 0 evidence and flags
+ *     restart, as in sdm_vmap_repose.  (In mode UNOBSERVED the never-observed entries still go.)
+ *   - No memory of R: a later integrate, observe or import with a retired tag is accepted as before.
+ * Everything is copied bits and integer scans: every output is bitwise the same from run to run, whatever the table
+ * layout.
+ * Errors, all raised before anything changes (a refused call leaves all four infos, a full fetch, the log, the camera
+ * lists, the evidence and the flags as they were):
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: a NULL ctx or delta; n_tags < 0; NULL tags with n_tags > 0; a tag outside [0, 2^31); a tag listed twice;
+ *     mode, carry or commit not 0 or 1; a negative capacity of a given array; a misaligned device pointer;
+ *     dropped_published without dropped_ids or removed_tag without removed_entry; a capacity smaller than the count it has
+ *     to hold (remap_capacity < M, dropped_capacity < dropped, removed_capacity < removed, with a non-NULL array): all
+ *     counts are filled, no array is written, nothing changes -- size the arrays and call again.  The counts come from a
+ *     read-only marking phase that ends in the first host wait.
+ *   SDM_EHIP: an allocation failure -- everything is allocated before anything is written.
+ * On an argument or state refusal the outs are 0, except examined and observations_before once known.
+ * Changes no plane, flag, list or counter of the engine outside the map.
+ * Cost: R is sorted on the host and uploaded once (4 B per tag).  Marking: per old pair two passes (8 B read, one binary
+ * search, 1 B mark), per old entry one binary search and 6 B read, then tile counts and four scans.  Lists: one pass over
+ * the entry marks (4 B of remap per old entry, 5 B per dropped entry), one over the pair marks (8 B per removed pair).
+ * Commit: one 37 B record copied per survivor (with carry 17 B more), two memsets over the table and one key computed
+ * and inserted per survivor; two memsets over the set and the chains and one sdm_vmap_import_observations of the E old
+ * pairs through remap, in place.  Two host waits: the counts, the end.  For host lists 4 B per old entry, 5 B per dropped
+ * entry and 8 B per removed pair cross the link; with device lists nothing but R does.  Measured: DESIGN.md s.23.
+ * Memory: the peak extra is one second set of records (37 B per record of capacity), 2 B per old entry and 1 B per old
+ * pair of marks, 4 B per old entry for a remap that is not a device buffer of the caller's, the staging of host lists, and
+ * with carry a second set of counters and flags (17 B per record of capacity); the old sets are freed before the call
+ * returns.  The log and the set are rebuilt in their own storage with 4 B per old pair of scratch.  Table, set, log and
+ * records keep their capacity.
+ * Limits: the points that lost are gone -- a map after WINNER-retiring R is a subset of the map of integrating only the
+ * other keyframes, not equal to it; the multiplicity is NOT reduced, because the map does not know which keyframe added
+ * what; carried counters still contain the rays of retired keyframes; ids and log indices change and remap is the
+ * consumer's only bridge; one rank only per map; rebuilding evidence from the log's pairs is not part of this. */
+#define SDM_VMAP_RETIRE_WINNER 0
+#define SDM_VMAP_RETIRE_UNOBSERVED 1
+typedef struct {
+    /* in */
+    int mode;                      /* SDM_VMAP_RETIRE_WINNER (0) or SDM_VMAP_RETIRE_UNOBSERVED (1) */
+    int carry;                     /* 0: evidence counters and published flags restart at 0; 1: survivors keep theirs */
+    int on_device;                 /* 1: every array below is device memory of this context's GPU (4-byte aligned; u8: any) */
+    unsigned *remap;               /* [remap_capacity] or NULL: new id of old entry i, 0xFFFFFFFF if dropped */
+    long long remap_capacity;
+    unsigned *dropped_ids;         /* [dropped_capacity] or NULL: OLD ids of the dropped entries, ascending */
+    unsigned char *dropped_published; /* [dropped_capacity] or NULL: their published flag before the call */
+    long long dropped_capacity;
+    unsigned *removed_entry;       /* [removed_capacity] or NULL: OLD entry id of each removed pair on a SURVIVING entry, in old log order */
+    int *removed_tag;              /* [removed_capacity] or NULL */
+    long long removed_capacity;
+    /* out */
+    long long examined;            /* M before */
+    long long dropped, dropped_were_published, orphaned;
+    long long voxels;              /* M after */
+    long long observations_before, observations, removed;
+    long long published_total;     /* after the call */
+} sdm_vmap_retire_delta;
+int sdm_vmap_retire(sdm_ctx *ctx, int n_tags, const int *tags /*[n_tags], host*/, int commit, sdm_vmap_retire_delta *delta);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

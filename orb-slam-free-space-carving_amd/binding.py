@@ -157,6 +157,17 @@ class VmapReposeDelta(C.Structure):
                 ("observations", C.c_longlong)]
 
 
+class VmapRetireDelta(C.Structure):
+    """sdm_vmap_retire_delta"""
+    _fields_ = [("mode", C.c_int), ("carry", C.c_int), ("on_device", C.c_int), ("remap", C.c_void_p),
+                ("remap_capacity", C.c_longlong), ("dropped_ids", C.c_void_p), ("dropped_published", C.c_void_p),
+                ("dropped_capacity", C.c_longlong), ("removed_entry", C.c_void_p), ("removed_tag", C.c_void_p),
+                ("removed_capacity", C.c_longlong), ("examined", C.c_longlong), ("dropped", C.c_longlong),
+                ("dropped_were_published", C.c_longlong), ("orphaned", C.c_longlong), ("voxels", C.c_longlong),
+                ("observations_before", C.c_longlong), ("observations", C.c_longlong), ("removed", C.c_longlong),
+                ("published_total", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -187,6 +198,15 @@ VMAP_IMPORT_OUTS = ("total", "dropped", "first_created", "created", "updated")
 VMAP_OBS_IMPORT_OUTS = ("total", "rejected", "first_created", "created")
 # the outs of sdm_vmap_repose
 VMAP_REPOSE_OUTS = ("examined", "reposed", "moved", "dropped", "merged", "voxels", "observations_before", "observations")
+# sdm_vmap_retire: the modes, the outs, and the lists with (dtype, capacity field, count out)
+VMAP_RETIRE_MODES = {"winner": 0, "unobserved": 1}
+VMAP_RETIRE_OUTS = ("examined", "dropped", "dropped_were_published", "orphaned", "voxels", "observations_before",
+                    "observations", "removed", "published_total")
+VMAP_RETIRE_LISTS = {"remap": (np.uint32, "remap_capacity", "examined"),
+                     "dropped_ids": (np.uint32, "dropped_capacity", "dropped"),
+                     "dropped_published": (np.uint8, "dropped_capacity", "dropped"),
+                     "removed_entry": (np.uint32, "removed_capacity", "removed"),
+                     "removed_tag": (np.int32, "removed_capacity", "removed")}
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -266,6 +286,7 @@ SYMBOLS = [
                                   C.POINTER(VmapImportDelta)]),
     ("sdm_vmap_import_observations", C.c_int, [_ctx, C.c_longlong, C.POINTER(VmapObsImport)]),
     ("sdm_vmap_repose", C.c_int, [_ctx, C.c_int, _ip, _f32p, _f32p, C.POINTER(VmapReposeDelta)]),
+    ("sdm_vmap_retire", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.POINTER(VmapRetireDelta)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1479,6 +1500,75 @@ class Engine:
         res = {f: int(getattr(d, f)) for f in VMAP_REPOSE_OUTS}
         if dest is not None:
             res["remap"] = dest[:res["examined"]]
+        return res
+
+    def vmap_retire(self, tags, mode="winner", carry=False, commit=True, remap=True, dropped=True, removed=True):
+        """Retires the keyframe tags `tags` from the voxel map (sdm_vmap_retire).  mode "winner": an entry goes iff its
+        record's tag is retired; "unobserved": iff no pair of a live keyframe is left on it.  The retired pairs leave the
+        observation log, the survivors move up to their rank, and evidence counters and published flags restart at 0
+        (carry False) or stay with their survivors (carry True).  commit False computes everything and changes nothing.
+        Returns the outs {"examined", "dropped", "dropped_were_published", "orphaned", "voxels", "observations_before",
+        "observations", "removed", "published_total"} and the lists "remap" (uint32[examined]: new id of every old entry,
+        0xFFFFFFFF for a dropped one), "dropped_ids" / "dropped_published" (uint32 / uint8 [dropped]: OLD ids, ascending,
+        and their flag before the call) and "removed_entry" / "removed_tag" (uint32 / int32 [removed]: the retired pairs of
+        surviving entries, OLD entry ids, old log order).  remap: True -- a NumPy array is made here; False -- not returned;
+        or the destination.  dropped: True, False or {"dropped_ids": dest, "dropped_published": dest}; removed: True, False
+        or {"removed_entry": dest, "removed_tag": dest} (the second of each is optional).  A destination is an array of the
+        list's dtype (pageable, or pinned from host_alloc) or a torch device tensor of as many bytes per element; all given
+        destinations are of one kind, and with device tensors no list is made here (give it or pass False).  Arrays made
+        here are sized again and the call repeated when the counts exceed them; a caller's destination too small raises
+        SdmError with the outs as attributes, and nothing has changed then."""
+        if mode not in VMAP_RETIRE_MODES:
+            raise ValueError("mode: need one of %s" % (sorted(VMAP_RETIRE_MODES),))
+        tg = np.ascontiguousarray(np.asarray([] if tags is None else tags, dtype=np.int32).reshape(-1))
+        n = len(tg)
+        dests, made = {}, set()
+        for arg, names, val in (("remap", ("remap",), remap), ("dropped", ("dropped_ids", "dropped_published"), dropped),
+                                ("removed", ("removed_entry", "removed_tag"), removed)):
+            if val is True:
+                made.update(names)
+            elif val is not False and val is not None:
+                given = {"remap": val} if arg == "remap" else dict(val)
+                for f, a in given.items():
+                    if f not in names:
+                        raise ValueError("unknown list %r in %s" % (f, arg))
+                    if a is not None:
+                        dests[f] = a
+        d = VmapRetireDelta()
+        d.mode, d.carry = VMAP_RETIRE_MODES[mode], int(carry)
+        kinds, caps = set(), {}
+        for f, a in dests.items():  # (two lists that share a capacity get the smaller one's)
+            ptr, cap = self._dest(f, a, VMAP_RETIRE_LISTS[f][0], 1, kinds)
+            setattr(d, f, ptr)
+            capf = VMAP_RETIRE_LISTS[f][1]
+            caps[capf] = min(cap, caps.get(capf, cap))
+            setattr(d, capf, caps[capf])
+        if len(kinds) > 1 or (kinds == {"device"} and made):
+            raise ValueError("the lists mix host arrays and device tensors")
+        d.on_device = 1 if kinds == {"device"} else 0
+        if made:  # M entries at most are dropped; the removed pairs are guessed and sized again on a refusal
+            m, e = self.vmap_info()["voxels"], self.vmap_obs_info()["observations"]
+            size = {"examined": max(m, 1), "dropped": max(m, 1), "removed": max(e // 4, 1)}
+        while True:
+            for f in made:
+                dt, capf, cnt = VMAP_RETIRE_LISTS[f]
+                dests[f] = np.empty(size[cnt], dt)
+                setattr(d, f, dests[f].ctypes.data)
+                setattr(d, capf, size[cnt])
+            rc = self.lib.sdm_vmap_retire(self.ctx, n, tg.ctypes.data_as(_ip) if n else None, int(commit), C.byref(d))
+            short = {cnt for cnt in (VMAP_RETIRE_LISTS[f][2] for f in made) if int(getattr(d, cnt)) > size[cnt]}
+            if not (rc and short):
+                break
+            for cnt in short:
+                size[cnt] = int(getattr(d, cnt))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            for f in VMAP_RETIRE_OUTS:
+                setattr(e, f, int(getattr(d, f)))
+            raise e
+        res = {f: int(getattr(d, f)) for f in VMAP_RETIRE_OUTS}
+        for f, a in dests.items():
+            res[f] = a[:res[VMAP_RETIRE_LISTS[f][2]]]
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):

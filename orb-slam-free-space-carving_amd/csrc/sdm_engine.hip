@@ -41,6 +41,7 @@
 #include "sdm_vmap_class.h"
 #include "sdm_vmap_import.h"
 #include "sdm_vmap_repose.h"
+#include "sdm_vmap_retire.h"
 
 using namespace sdm;
 
@@ -4299,7 +4300,8 @@ int sdm_vmap_import_observations(sdm_ctx* c, long long count, sdm_vmap_obs_impor
     const long long pblocks = (P + BLOCK - 1) / BLOCK;
     for (long long b0 = 0; b0 < pblocks; b0 += per)
         hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, d_entry,
-                           d_tag, d_map, io->map_count, P, b0 * BLOCK, (unsigned)v.M, o.tb, d_where, d_ctr);
+                           d_tag, d_map, io->map_count, P, b0 * BLOCK, (unsigned)v.M, o.tb, d_where, d_ctr,
+                           (const unsigned char*)nullptr);
     for (long long t0 = 0; t0 < vt; t0 += per)
         hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_where, P, t0,
                            d_cnt);
@@ -4552,7 +4554,7 @@ int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, co
         for (long long b0 = 0; b0 < eblocks; b0 += per)
             hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
                                (const unsigned*)o.log.entry, (const int*)o.log.tag, (const unsigned*)d_remap, M, E, b0 * BLOCK,
-                               (unsigned)M2, o.tb, d_owhere, d_octr);
+                               (unsigned)M2, o.tb, d_owhere, d_octr, (const unsigned char*)nullptr);
         for (long long t0 = 0; t0 < ot; t0 += per)
             hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_owhere, E, t0,
                                d_ocnt);
@@ -4588,6 +4590,310 @@ int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, co
     delta->voxels = M2;
     delta->merged = M - dropped - M2;
     delta->observations = o.E;
+    return SDM_OK;
+}
+
+// ---- retiring keyframes from the persistent voxel map (sdm_vmap_retire.h) -------------------------------------------------
+int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vmap_retire_delta* delta)
+{
+    if (delta)
+        delta->examined = delta->dropped = delta->dropped_were_published = delta->orphaned = delta->voxels =
+            delta->observations_before = delta->observations = delta->removed = delta->published_total = 0;
+    if (!c || !delta) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    if (n_tags < 0) return fail(SDM_EINVAL, "negative n_tags");
+    if (n_tags > 0 && !tags) return fail(SDM_EINVAL, "null tags");
+    if (delta->mode != SDM_VMAP_RETIRE_WINNER && delta->mode != SDM_VMAP_RETIRE_UNOBSERVED)
+        return fail(SDM_EINVAL, "mode must be SDM_VMAP_RETIRE_WINNER or SDM_VMAP_RETIRE_UNOBSERVED");
+    if (delta->carry != 0 && delta->carry != 1) return fail(SDM_EINVAL, "carry must be 0 or 1");
+    if (commit != 0 && commit != 1) return fail(SDM_EINVAL, "commit must be 0 or 1");
+    const size_t nt = (size_t)n_tags;
+    std::vector<int> sorted;  // R, ascending
+    try {
+        sorted.assign(tags, tags + nt);
+    } catch (const std::bad_alloc&) {
+        return fail(SDM_EHIP, "host allocation for the tags failed");
+    }
+    for (size_t p = 0; p < nt; p++)
+        if (sorted[p] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t p = 1; p < nt; p++)
+        if (sorted[p] == sorted[p - 1]) return fail(SDM_EINVAL, "tag " + std::to_string(sorted[p]) + " listed twice");
+    unsigned *remap_dst = delta->remap, *drop_dst = delta->dropped_ids, *rem_dst = delta->removed_entry;
+    unsigned char* dpub_dst = delta->dropped_published;
+    int* rtag_dst = delta->removed_tag;
+    if ((remap_dst && delta->remap_capacity < 0) || ((drop_dst || dpub_dst) && delta->dropped_capacity < 0) ||
+        ((rem_dst || rtag_dst) && delta->removed_capacity < 0))
+        return fail(SDM_EINVAL, "negative capacity");
+    if (dpub_dst && !drop_dst) return fail(SDM_EINVAL, "dropped_published without dropped_ids");
+    if (rtag_dst && !rem_dst) return fail(SDM_EINVAL, "removed_tag without removed_entry");
+    const bool dev = delta->on_device != 0;
+    if (dev && ((uintptr_t)remap_dst | (uintptr_t)drop_dst | (uintptr_t)rem_dst | (uintptr_t)rtag_dst) % 4)
+        return fail(SDM_EINVAL, "device buffer not aligned (remap, dropped_ids, removed_entry, removed_tag: 4 B)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const long long M = v.M, E = o.E;
+    const bool unobserved = delta->mode == SDM_VMAP_RETIRE_UNOBSERVED, carry = delta->carry == 1;
+    delta->examined = M;
+    delta->observations_before = E;
+    if (M == 0) {  // (no entry: no pair, no counter, no flag)
+        if (commit) v.calls++;
+        return SDM_OK;
+    }
+
+    // the marking phase's scratch and the log's, R on both sides of the link, the second sets: everything but the staging
+    // of host lists, which follows the counts, is allocated before anything is written
+    const size_t m = (size_t)M, e = (size_t)E;
+    const long long vt = (M + EXT_TILE - 1) / EXT_TILE;
+    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t tags_b = ext_align(4 * std::max(nt, (size_t)1)), mark_b = ext_align(m), tcnt_b = ext_align(4 * (size_t)vt),
+                 toff_b = ext_align(4 * (size_t)(vt + 1)), blk_b = ext_align(8 * (size_t)vb);
+    const bool remap_own = !(dev && remap_dst);
+    int rc;
+    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes,
+                           512 + tags_b + 2 * mark_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b + (remap_own ? ext_align(4 * m) : 0))))
+        return rc;
+    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tags_b))) return rc;
+    const long long ot = (E + EXT_TILE - 1) / EXT_TILE;
+    const long long ob = (ot + 1 + EXT_SCAN - 1) / EXT_SCAN;
+    const size_t owhere_b = ext_align(4 * e), omark_b = ext_align(e), otcnt_b = ext_align(4 * (size_t)ot),
+                 otoff_b = ext_align(4 * (size_t)(ot + 1)), oblk_b = ext_align(8 * (size_t)ob);
+    if (E > 0) {
+        if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, 512 + owhere_b + omark_b + 2 * otcnt_b + 2 * otoff_b + 4 * oblk_b)))
+            return rc;
+        if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
+    }
+    VrepBlocks nb;
+    VmapRecords nr{};
+    unsigned long long *ncr = nullptr, *nen = nullptr;
+    if (commit) {
+        if ((rc = vmap_make_records(v.rec_cap, &nb.rec, &nr))) return rc;
+        if (carry && v.d_evid && (rc = vmap_make_evidence(c, v.rec_cap, &nb.evid, &ncr, &nen))) return rc;
+        if (carry && v.cls.d_pub && (rc = vmap_make_published(c, v.rec_cap, &nb.pub))) return rc;
+    }
+
+    unsigned char* p = v.d_scratch;
+    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                            // {-, overflow}
+    unsigned long long* d_cnt3 = reinterpret_cast<unsigned long long*>(p + 64);  // k_vret_entries' three counters
+    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // k_vret_totals' seven
+    p += 512;
+    int* d_tags = reinterpret_cast<int*>(p);
+    p += tags_b;
+    unsigned char* d_seen = p;
+    p += mark_b;
+    unsigned char* d_emark = p;
+    p += mark_b;
+    unsigned* d_cnt_s = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_cnt_d = reinterpret_cast<unsigned*>(p);
+    p += tcnt_b;
+    unsigned* d_off_s = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned* d_off_d = reinterpret_cast<unsigned*>(p);
+    p += toff_b;
+    unsigned long long* d_bsum_s = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_s = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_bsum_d = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned long long* d_boff_d = reinterpret_cast<unsigned long long*>(p);
+    p += blk_b;
+    unsigned* d_remap = remap_own ? reinterpret_cast<unsigned*>(p) : remap_dst;
+    // the log's scratch: the import's part first (as sdm_vmap_repose lays it out), then the marks and their two scans
+    unsigned long long *d_octr = nullptr, *d_otot = nullptr, *d_obsum = nullptr, *d_oboff = nullptr;
+    unsigned long long *d_bsum_r = nullptr, *d_boff_r = nullptr, *d_bsum_v = nullptr, *d_boff_v = nullptr;
+    unsigned *d_owhere = nullptr, *d_ocnt = nullptr, *d_ooff = nullptr, *d_cnt_r = nullptr, *d_cnt_v = nullptr, *d_off_r = nullptr,
+             *d_off_v = nullptr;
+    unsigned char* d_pmark = nullptr;
+    if (E > 0) {
+        unsigned char* q = o.d_scratch;
+        d_octr = reinterpret_cast<unsigned long long*>(q + 64);   // {rejected, stored or found, overflow}
+        d_otot = reinterpret_cast<unsigned long long*>(q + 256);  // {created, rejected, stored or found, overflow}
+        q += 512;
+        d_owhere = reinterpret_cast<unsigned*>(q);
+        q += owhere_b;
+        d_ocnt = reinterpret_cast<unsigned*>(q);
+        q += otcnt_b;
+        d_ooff = reinterpret_cast<unsigned*>(q);
+        q += otoff_b;
+        d_obsum = reinterpret_cast<unsigned long long*>(q);
+        q += oblk_b;
+        d_oboff = reinterpret_cast<unsigned long long*>(q);
+        q += oblk_b;
+        d_pmark = q;
+        q += omark_b;
+        d_cnt_r = d_ocnt, d_off_r = d_ooff, d_bsum_r = d_obsum, d_boff_r = d_oboff;  // (the import's are free until the log is rebuilt)
+        d_cnt_v = reinterpret_cast<unsigned*>(q);
+        q += otcnt_b;
+        d_off_v = reinterpret_cast<unsigned*>(q);
+        q += otoff_b;
+        d_bsum_v = reinterpret_cast<unsigned long long*>(q);
+        q += oblk_b;
+        d_boff_v = reinterpret_cast<unsigned long long*>(q);
+    }
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
+    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
+    if (nt) std::memcpy(h_tags, sorted.data(), 4 * nt);
+
+    // the marking phase: reads the map, writes scratch
+    HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 512, c->stream));
+    if (nt) HIP_TRY(hipMemcpyAsync(d_tags, h_tags, 4 * nt, hipMemcpyHostToDevice, c->stream));
+    if (unobserved) HIP_TRY(hipMemsetAsync(d_seen, 0, m, c->stream));
+    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
+    const long long pblocks = (M + BLOCK - 1) / BLOCK, eblocks = (E + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < eblocks; b0 += per)
+        hipLaunchKernelGGL(k_vret_pairs, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
+                           (const unsigned*)o.log.entry, (const int*)o.log.tag, E, b0 * BLOCK, (unsigned)M, (const int*)d_tags, n_tags,
+                           d_pmark, unobserved ? d_seen : (unsigned char*)nullptr);
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vret_entries, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream,
+                           (const int*)v.rec.tag, (const unsigned char*)v.cls.d_pub,
+                           unobserved ? (const unsigned char*)d_seen : (const unsigned char*)nullptr, M, b0 * BLOCK,
+                           (const int*)d_tags, n_tags, d_emark, d_cnt3);
+    for (long long t0 = 0; t0 < vt; t0 += per)
+        hipLaunchKernelGGL(k_vret_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream,
+                           (const unsigned char*)d_emark, 1u, 1u, 0u, M, t0, d_cnt_s, d_cnt_d);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_s, vt, d_off_s, d_bsum_s);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_s, (int)vb, d_boff_s);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_d, vt, d_off_d, d_bsum_d);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_d, (int)vb, d_boff_d);
+    if (E > 0) {
+        for (long long b0 = 0; b0 < eblocks; b0 += per)
+            hipLaunchKernelGGL(k_vret_vanish, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
+                               (const unsigned*)o.log.entry, E, b0 * BLOCK, (unsigned)M, (const unsigned char*)d_emark, d_pmark);
+        for (long long t0 = 0; t0 < ot; t0 += per)
+            hipLaunchKernelGGL(k_vret_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream,
+                               (const unsigned char*)d_pmark, 3u, (unsigned)VRET_REMOVED, (unsigned)VRET_VANISHED, E, t0, d_cnt_r,
+                               d_cnt_v);
+        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_cnt_r, ot, d_off_r, d_bsum_r);
+        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_r, (int)ob, d_boff_r);
+        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_cnt_v, ot, d_off_v, d_bsum_v);
+        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_v, (int)ob, d_boff_v);
+    }
+    hipLaunchKernelGGL(k_vret_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_s, d_boff_s, d_off_d, d_boff_d, E > 0 ? ot : 0ll,
+                       d_off_r, d_boff_r, d_off_v, d_boff_v, d_cnt3, d_tot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: the counts
+    const long long M2 = (long long)h_tot[0], dropped = (long long)h_tot[1], removed = (long long)h_tot[2],
+                    vanished = (long long)h_tot[3];
+    delta->dropped = dropped;
+    delta->removed = removed;
+    delta->orphaned = (long long)h_tot[4];
+    delta->dropped_were_published = (long long)h_tot[5];
+    delta->voxels = M2;
+    delta->observations = E - removed - vanished;
+    delta->published_total = carry ? (long long)h_tot[6] : 0;
+    if (remap_dst && delta->remap_capacity < M)
+        return fail(SDM_EINVAL, "remap_capacity " + std::to_string(delta->remap_capacity) + " < entries = " + std::to_string(M) +
+                                    " (the counts are filled)");
+    if (drop_dst && delta->dropped_capacity < dropped)
+        return fail(SDM_EINVAL, "dropped_capacity " + std::to_string(delta->dropped_capacity) + " < " + std::to_string(dropped) +
+                                    " dropped entries (the counts are filled)");
+    if (rem_dst && delta->removed_capacity < removed)
+        return fail(SDM_EINVAL, "removed_capacity " + std::to_string(delta->removed_capacity) + " < " + std::to_string(removed) +
+                                    " removed pairs (the counts are filled)");
+
+    // the lists (nothing of the map has changed yet: a failure here leaves the state as it was)
+    const bool list_drop = drop_dst && dropped, list_rem = rem_dst && removed;
+    unsigned *d_drop = list_drop ? drop_dst : nullptr, *d_rem = list_rem ? rem_dst : nullptr;
+    unsigned char* d_dpub = list_drop ? dpub_dst : nullptr;
+    int* d_rtag = list_rem ? rtag_dst : nullptr;
+    if (!dev && (list_drop || list_rem)) {
+        const size_t drop_b = list_drop ? ext_align(4 * (size_t)dropped) : 0, dpub_b = list_drop && dpub_dst ? ext_align((size_t)dropped) : 0,
+                     rem_b = list_rem ? ext_align(4 * (size_t)removed) : 0;
+        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, drop_b + dpub_b + 2 * rem_b))) return rc;
+        if (list_drop) d_drop = reinterpret_cast<unsigned*>(v.d_out);
+        if (list_drop && dpub_dst) d_dpub = v.d_out + drop_b;
+        if (list_rem) d_rem = reinterpret_cast<unsigned*>(v.d_out + drop_b + dpub_b);
+        if (list_rem && rtag_dst) d_rtag = reinterpret_cast<int*>(v.d_out + drop_b + dpub_b + rem_b);
+    }
+    if (commit || remap_dst || list_drop)
+        for (long long t0 = 0; t0 < vt; t0 += per)
+            hipLaunchKernelGGL(k_vret_remap, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream,
+                               (const unsigned char*)d_emark, M, t0, d_off_s, d_boff_s, d_off_d, d_boff_d,
+                               commit || remap_dst ? d_remap : (unsigned*)nullptr, d_drop, d_dpub);
+    if (list_rem)
+        for (long long t0 = 0; t0 < ot; t0 += per)
+            hipLaunchKernelGGL(k_vret_removed, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream,
+                               (const unsigned char*)d_pmark, (const unsigned*)o.log.entry, (const int*)o.log.tag, E, t0, d_off_r,
+                               d_boff_r, d_rem, d_rtag);
+    HIP_TRY(hipGetLastError());
+    if (!dev) {  // (the copies are queued behind the kernels that fill their sources and before anything overwrites them)
+        if (remap_dst) HIP_TRY(hipMemcpyAsync(remap_dst, d_remap, 4 * m, hipMemcpyDeviceToHost, c->stream));
+        if (list_drop) HIP_TRY(hipMemcpyAsync(drop_dst, d_drop, 4 * (size_t)dropped, hipMemcpyDeviceToHost, c->stream));
+        if (list_drop && dpub_dst) HIP_TRY(hipMemcpyAsync(dpub_dst, d_dpub, (size_t)dropped, hipMemcpyDeviceToHost, c->stream));
+        if (list_rem) HIP_TRY(hipMemcpyAsync(rem_dst, d_rem, 4 * (size_t)removed, hipMemcpyDeviceToHost, c->stream));
+        if (list_rem && rtag_dst) HIP_TRY(hipMemcpyAsync(rtag_dst, d_rtag, 4 * (size_t)removed, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!commit) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SDM_OK;
+    }
+
+    // records (with carry: counters and flags) into the second set; the table emptied and filled from the new records
+    for (long long b0 = 0; b0 < pblocks; b0 += per)
+        hipLaunchKernelGGL(k_vret_records, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.rec, nr,
+                           (const unsigned*)d_remap, M, b0 * BLOCK, nb.evid ? (const unsigned long long*)v.crossings : nullptr,
+                           nb.evid ? (const unsigned long long*)v.ends : nullptr, ncr, nen,
+                           nb.pub ? (const unsigned char*)v.cls.d_pub : nullptr, nb.pub);
+    if (!carry) {
+        if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, 2 * ext_align(8 * (size_t)v.rec_cap), c->stream));
+        if (v.cls.d_pub) HIP_TRY(hipMemsetAsync(v.cls.d_pub, 0, (size_t)v.rec_cap, c->stream));
+    }
+    HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
+    HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
+    const long long nblocks = (M2 + BLOCK - 1) / BLOCK;
+    for (long long b0 = 0; b0 < nblocks; b0 += per)
+        hipLaunchKernelGGL(k_vret_table, dim3((unsigned)std::min(per, nblocks - b0)), dim3(BLOCK), 0, c->stream, (const float*)nr.xyz,
+                           M2, b0 * BLOCK, v.inv, v.tb, d_ctr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot + 8, d_ctr, 8, hipMemcpyDeviceToHost, c->stream));
+
+    // the log: the old pairs that stay, in log order, through remap into the emptied set, in place
+    unsigned long long* h_otot = nullptr;
+    if (E > 0) {
+        const size_t b4 = ext_align(4 * (size_t)v.rec_cap);
+        HIP_TRY(hipMemsetAsync(o.d_table, 0xff, 20 * (size_t)o.cap, c->stream));
+        HIP_TRY(hipMemsetAsync(o.d_ent, 0xff, b4, c->stream));
+        HIP_TRY(hipMemsetAsync(o.d_ent + b4, 0, b4, c->stream));
+        HIP_TRY(hipMemsetAsync(d_octr, 0, 24, c->stream));
+        for (long long b0 = 0; b0 < eblocks; b0 += per)
+            hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
+                               (const unsigned*)o.log.entry, (const int*)o.log.tag, (const unsigned*)d_remap, M, E, b0 * BLOCK,
+                               (unsigned)M2, o.tb, d_owhere, d_octr, (const unsigned char*)d_pmark);
+        for (long long t0 = 0; t0 < ot; t0 += per)
+            hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_owhere, E, t0,
+                               d_ocnt);
+        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_ocnt, ot, d_ooff, d_obsum);
+        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_obsum, (int)ob, d_oboff);
+        hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, ot, d_ooff, d_oboff, d_octr, d_otot);
+        for (long long t0 = 0; t0 < ot; t0 += per)
+            hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log,
+                               o.last_obs, o.ncam, d_owhere, 0u, E, t0, d_ooff, d_oboff);
+        HIP_TRY(hipGetLastError());
+        h_otot = reinterpret_cast<unsigned long long*>(o.h_pin);
+        HIP_TRY(hipMemcpyAsync(h_otot, d_otot, 32, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end
+    if (reinterpret_cast<unsigned*>(h_tot + 8)[1]) return fail(SDM_EHIP, "voxel map table overflow");
+    if (h_otot && h_otot[3]) return fail(SDM_EHIP, "observation set overflow");
+
+    // the second sets become the map's; the old ones go with `nb`
+    std::swap(v.d_rec, nb.rec);
+    v.rec = nr;
+    if (nb.evid) {
+        std::swap(v.d_evid, nb.evid);
+        v.crossings = ncr;
+        v.ends = nen;
+    }
+    if (nb.pub) std::swap(v.cls.d_pub, nb.pub);
+    v.cls.published = delta->published_total;
+    v.M = M2;
+    v.calls++;
+    if (h_otot) o.E = (long long)h_otot[0];
     return SDM_OK;
 }
 

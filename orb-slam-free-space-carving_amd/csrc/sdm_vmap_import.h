@@ -180,17 +180,20 @@ __global__ __launch_bounds__(BLOCK) void k_vimp_write(VmapTable tb, VmapRecords 
     rec.epoch[e] = src_epoch ? src_epoch[r] : epoch;
 }
 
-// pairs k0 + thread; ctr = {rejected pairs, stored or found pairs, overflow} (k_vobs_totals' layout)
+// pairs k0 + thread; ctr = {rejected pairs, stored or found pairs, overflow} (k_vobs_totals' layout).  skip
+// (sdm_vmap_retire: the pairs that leave the log) rejects pair k where skip[k] != 0
 __global__ __launch_bounds__(BLOCK) void k_vobs_import_insert(const unsigned* __restrict__ entry, const int* __restrict__ tag,
                                                               const unsigned* __restrict__ entry_map, long long map_count,
                                                               long long P, long long k0, unsigned M, VobsTable ot,
-                                                              unsigned* __restrict__ where, unsigned long long* __restrict__ ctr)
+                                                              unsigned* __restrict__ where, unsigned long long* __restrict__ ctr,
+                                                              const unsigned char* __restrict__ skip)
 {
     const long long k = k0 + (long long)blockIdx.x * BLOCK + threadIdx.x;
     bool rejected = false, cand = false;
     if (k < P) {
         unsigned id = entry[k];
         if (entry_map) id = (long long)id < map_count ? entry_map[id] : VMAP_NOID;
+        if (skip && skip[k]) id = VMAP_NOID;
         const int t = tag[k];
         unsigned w = VOX_NONE;
         if (id >= M || t < 0) {
