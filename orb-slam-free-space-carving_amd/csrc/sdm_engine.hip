@@ -647,6 +647,27 @@ void for_ref_slices(int n_ref, long long blocks_per_ref, int threads, F&& fn)
     for (int first = 0; first < n_ref; first += per) fn(first, std::min(per, n_ref - first));
 }
 
+// The same limit (the comment above for_ref_slices) for a grid that grows with points, tiles or table slots: `blocks`
+// workgroups of `threads` work-items go out in dispatches of at most 2^31 work-items, fn(first_block, grid) launches one.
+template <typename F>
+void launch_sliced(long long blocks, F&& fn, int threads = BLOCK)
+{
+    const long long per = (1ll << 31) / threads;
+    for (long long b0 = 0; b0 < blocks; b0 += per) fn(b0, (unsigned)std::min(per, blocks - b0));
+}
+
+// workgroups of k_extract_scan_tiles over the tiles + 1 offsets of `tiles` per-tile counts: what bsum and boff hold
+inline long long scan_blocks(long long tiles) { return (tiles + 1 + EXT_SCAN - 1) / EXT_SCAN; }
+
+// exclusive scan of cnt[tiles] in two levels: off[tiles + 1] within each scan workgroup, boff[scan_blocks(tiles)] across them
+inline void scan_counts(sdm_ctx* c, const unsigned* cnt, long long tiles, unsigned* off, unsigned long long* bsum,
+                        unsigned long long* boff)
+{
+    const long long nb = scan_blocks(tiles);
+    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, cnt, tiles, off, bsum);
+    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, bsum, (int)nb, boff);
+}
+
 // HIP events around one stage's launches, on the stream the kernels run on
 struct StageTimer {
     sdm_ctx* c;
@@ -2359,8 +2380,7 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
     in.rho_min = ext_float_floor(min_rho);
     HIP_TRY(hipMemcpyAsync(d_tab, h_tab, sizeof(ExtractSlot) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_extract_count, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_cnt);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, d_cnt, nt, d_toff, d_bsum);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)nb, d_boff);
+    scan_counts(c, d_cnt, nt, d_toff, d_bsum, d_boff);
     hipLaunchKernelGGL(k_extract_offsets, dim3(blocks_for(n + 1)), dim3(BLOCK), 0, c->stream, d_tab, n, nt, d_toff, d_boff,
                        d_offs);
     HIP_TRY(hipGetLastError());
@@ -2414,10 +2434,10 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
         }
         h_cut[n] = blocks;
         HIP_TRY(hipMemcpyAsync(d_cut, h_cut, sizeof(long long) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
-        const long long per = (1ll << 31) / SUP_BLOCK;  // work-items of one dispatch (for_ref_slices)
-        for (long long b0 = 0; b0 < blocks; b0 += per)
-            hipLaunchKernelGGL(k_point_support, dim3((unsigned)std::min(per, blocks - b0)), dim3(SUP_BLOCK), 0, c->stream,
-                               c->pool, c->P, c->d_refs, c->d_pairs, n, n_nbr, c->W, c->H, d_cut, b0, d_offs, dst.pixel, d_sup);
+        launch_sliced(blocks, [&](long long b0, unsigned g) {
+            hipLaunchKernelGGL(k_point_support, dim3(g), dim3(SUP_BLOCK), 0, c->stream, c->pool, c->P, c->d_refs, c->d_pairs, n,
+                               n_nbr, c->W, c->H, d_cut, b0, d_offs, dst.pixel, d_sup);
+        }, SUP_BLOCK);
         HIP_TRY(hipGetLastError());
         if (st) st->d_support = d_sup, st->d_block0 = d_cut, st->blocks = blocks;
     }
@@ -2547,16 +2567,15 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
 
     HIP_TRY(hipMemsetAsync(tb.keys, 0xff, 2 * key_b, c->stream));  // keys: VOX_EMPTY; values: the minimum's identity
     HIP_TRY(hipMemsetAsync(tb.cnt, 0, cnt_b, c->stream));           // counts and the flag
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
     const long long pblocks = (T + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_voxel_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, st.at.xyz,
-                           st.at.rho_sigma, T, b0 * BLOCK, inv, tb, d_where, d_flag);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_voxel_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0,
-                           d_tcnt);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_tcnt, vt, d_toff, d_bsum);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)vb, d_boff);
+    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+        hipLaunchKernelGGL(k_voxel_insert, dim3(g), dim3(BLOCK), 0, c->stream, st.at.xyz, st.at.rho_sigma, T, b0 * BLOCK, inv, tb,
+                           d_where, d_flag);
+    });
+    launch_sliced(vt, [&](long long t0, unsigned g) {
+        hipLaunchKernelGGL(k_voxel_count, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0, d_tcnt);
+    });
+    scan_counts(c, d_tcnt, vt, d_toff, d_bsum, d_boff);
     hipLaunchKernelGGL(k_voxel_offsets, dim3((unsigned)(n + 2)), dim3(BLOCK), 0, c->stream, tb, d_where, T, st.d_offsets, n, vt,
                        d_toff, d_boff, d_flag, d_voffs);
     HIP_TRY(hipGetLastError());
@@ -2681,32 +2700,30 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
             HIP_TRY(hipMemcpyAsync(d_org, c->h_vcam + 256 + ext_align(4 * cam_tab_n), 16 * (size_t)Cn, hipMemcpyHostToDevice,
                                    c->stream));
     }
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_voxel_write, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0,
-                           d_toff, d_boff, st.at, dst, d_mult, d_sidx, d_rank);
+    launch_sliced(vt, [&](long long t0, unsigned g) {
+        hipLaunchKernelGGL(k_voxel_write, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0, d_toff, d_boff, st.at, dst,
+                           d_mult, d_sidx, d_rank);
+    });
     if (d_rank)
-        for (long long b0 = 0; b0 < pblocks; b0 += per)
-            hipLaunchKernelGGL(k_voxel_rep, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, tb, d_where,
-                               T, b0 * BLOCK, d_rank);
+        launch_sliced(pblocks, [&](long long b0, unsigned g) {
+            hipLaunchKernelGGL(k_voxel_rep, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, b0 * BLOCK, d_rank);
+        });
     HIP_TRY(hipGetLastError());
     if (cams) {
         // SDM_VOXCAM_PLAIN_OR: one atomic per lane and word instead of one per run of equal rank (A/B; the same bits)
         const bool plain_or = getenv("SDM_VOXCAM_PLAIN_OR") != nullptr;
-        const long long sper = (1ll << 31) / SUP_BLOCK;
-        for (long long b0 = 0; b0 < st.blocks; b0 += sper) {
-            const dim3 grid((unsigned)std::min(sper, st.blocks - b0));
+        launch_sliced(st.blocks, [&](long long b0, unsigned g) {
             if (plain_or)
-                hipLaunchKernelGGL(k_voxcam_or<false>, grid, dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
+                hipLaunchKernelGGL(k_voxcam_or<false>, dim3(g), dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
                                    st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
             else
-                hipLaunchKernelGGL(k_voxcam_or<true>, grid, dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
+                hipLaunchKernelGGL(k_voxcam_or<true>, dim3(g), dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
                                    st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
-        }
-        for (long long t0 = 0; t0 < kt; t0 += per)
-            hipLaunchKernelGGL(k_voxcam_count, dim3((unsigned)std::min(per, kt - t0)), dim3(BLOCK), 0, c->stream, d_bits, Wd, M,
-                               t0, d_ktcnt);
-        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)kb), dim3(BLOCK), 0, c->stream, d_ktcnt, kt, d_ktoff, d_kbsum);
-        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_kbsum, (int)kb, d_kboff);
+        }, SUP_BLOCK);
+        launch_sliced(kt, [&](long long t0, unsigned g) {
+            hipLaunchKernelGGL(k_voxcam_count, dim3(g), dim3(BLOCK), 0, c->stream, d_bits, Wd, M, t0, d_ktcnt);
+        });
+        scan_counts(c, d_ktcnt, kt, d_ktoff, d_kbsum, d_kboff);
         // (with no slot, k_extract_offsets writes the one entry offsets[0] = the offset of tile kt: the total)
         hipLaunchKernelGGL(k_extract_offsets, dim3(1), dim3(BLOCK), 0, c->stream, (const ExtractSlot*)nullptr, 0, kt, d_ktoff,
                            d_kboff, d_E);
@@ -2737,9 +2754,10 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
             else if (!out->on_device) d_cslots = nullptr;
             if (cross_b) d_cross = reinterpret_cast<unsigned*>(c->d_vcam_out + off_b + slots_b);
         }
-        for (long long t0 = 0; t0 < kt; t0 += per)
-            hipLaunchKernelGGL(k_voxcam_write, dim3((unsigned)std::min(per, kt - t0)), dim3(BLOCK), 0, c->stream, d_bits, Wd, M,
-                               t0, d_ktoff, d_kboff, ctab.slot_of_cam, d_coff, d_cslots);
+        launch_sliced(kt, [&](long long t0, unsigned g) {
+            hipLaunchKernelGGL(k_voxcam_write, dim3(g), dim3(BLOCK), 0, c->stream, d_bits, Wd, M, t0, d_ktoff, d_kboff,
+                               ctab.slot_of_cam, d_coff, d_cslots);
+        });
         HIP_TRY(hipGetLastError());
         if (fs) {  // sdm_carve.h: one lane per list entry walks its ray through the table
             HIP_TRY(hipMemsetAsync(d_cross, 0, 4 * (size_t)M, c->stream));
@@ -2758,9 +2776,9 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
             in.end_margin = fs->end_margin;
             in.max_steps = fs->max_steps;
             const long long eblocks = (E + BLOCK - 1) / BLOCK;
-            for (long long b0 = 0; b0 < eblocks; b0 += per)
-                hipLaunchKernelGGL(k_voxel_carve, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in,
-                                   b0 * BLOCK, tb, d_cross, d_fs_tot);
+            launch_sliced(eblocks, [&](long long b0, unsigned g) {
+                hipLaunchKernelGGL(k_voxel_carve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, tb, d_cross, d_fs_tot);
+            });
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(c->h_vcam + 16, d_fs_tot, 16, hipMemcpyDeviceToHost, c->stream));
             if (!out->on_device) HIP_TRY(hipMemcpyAsync(fs->crossings, d_cross, 4 * (size_t)M, hipMemcpyDeviceToHost, c->stream));
@@ -2823,2079 +2841,8 @@ int sdm_extract_points_voxel_freespace(sdm_ctx* c, int n, const int* slots, int 
     return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, fs, offsets);
 }
 
-// ---- the persistent voxel map (sdm_vmap_*, sdm_vmap.h) -------------------------------------------------------------------
-// one block for the table: keys | cval | id | cfirst | ccnt (28 B per slot), set to empty keys / the reductions' identities
-static int vmap_make_table(sdm_ctx* c, unsigned long long cap, unsigned char** block, VmapTable* tb)
-{
-    const size_t n = (size_t)cap;
-    HIP_TRY(hipMalloc((void**)block, 28 * n));
-    unsigned char* p = *block;
-    tb->keys = reinterpret_cast<unsigned long long*>(p);
-    tb->cval = reinterpret_cast<unsigned long long*>(p + 8 * n);
-    tb->id = reinterpret_cast<unsigned*>(p + 16 * n);
-    tb->cfirst = reinterpret_cast<unsigned*>(p + 20 * n);
-    tb->ccnt = reinterpret_cast<unsigned*>(p + 24 * n);
-    tb->mask = cap - 1;
-    hipError_t e = hipMemsetAsync(p, 0xff, 24 * n, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(p + 24 * n, 0, 4 * n, c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(*block);
-        *block = nullptr;
-        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-    }
-    return SDM_OK;
-}
-
-// one block for the records of `cap` entries, every array 256-byte aligned
-static int vmap_make_records(long long cap, unsigned char** block, VmapRecords* r)
-{
-    const size_t n = (size_t)std::max(cap, 1ll);
-    const size_t b4 = ext_align(4 * n);
-    HIP_TRY(hipMalloc((void**)block, ext_align(12 * n) + ext_align(8 * n) + 4 * b4 + ext_align(n)));
-    unsigned char* p = *block;
-    r->xyz = reinterpret_cast<float*>(p), p += ext_align(12 * n);
-    r->rho_sigma = reinterpret_cast<float2*>(p), p += ext_align(8 * n);
-    r->pixel = reinterpret_cast<unsigned*>(p), p += b4;
-    r->tag = reinterpret_cast<int*>(p), p += b4;
-    r->multiplicity = reinterpret_cast<unsigned*>(p), p += b4;
-    r->epoch = reinterpret_cast<unsigned*>(p), p += b4;
-    r->intensity = p;
-    return SDM_OK;
-}
-
-// one block for the free-space counters of `cap` entries: crossings | ends, both zero
-static int vmap_make_evidence(sdm_ctx* c, long long cap, unsigned char** block, unsigned long long** crossings,
-                              unsigned long long** ends)
-{
-    const size_t b8 = ext_align(8 * (size_t)std::max(cap, 1ll));
-    HIP_TRY(hipMalloc((void**)block, 2 * b8));
-    *crossings = reinterpret_cast<unsigned long long*>(*block);
-    *ends = reinterpret_cast<unsigned long long*>(*block + b8);
-    const hipError_t e = hipMemsetAsync(*block, 0, 2 * b8, c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(*block);
-        *block = nullptr;
-        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-    }
-    return SDM_OK;
-}
-
-// one block for the observations' per-entry arrays of `cap` entries: last_obs (no observation) | ncam (0)
-static int vmap_make_obs_entries(sdm_ctx* c, long long cap, unsigned char** block, unsigned** last_obs, unsigned** ncam)
-{
-    const size_t b4 = ext_align(4 * (size_t)std::max(cap, 1ll));
-    HIP_TRY(hipMalloc((void**)block, 2 * b4));
-    *last_obs = reinterpret_cast<unsigned*>(*block);
-    *ncam = reinterpret_cast<unsigned*>(*block + b4);
-    hipError_t e = hipMemsetAsync(*block, 0xff, b4, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(*block + b4, 0, b4, c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(*block);
-        *block = nullptr;
-        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-    }
-    return SDM_OK;
-}
-
-// the published flags of `cap` entries, all 0
-static int vmap_make_published(sdm_ctx* c, long long cap, unsigned char** block)
-{
-    const size_t b = (size_t)std::max(cap, 1ll);
-    HIP_TRY(hipMalloc((void**)block, b));
-    const hipError_t e = hipMemsetAsync(*block, 0, b, c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(*block);
-        *block = nullptr;
-        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-    }
-    return SDM_OK;
-}
-
-static void vmap_free(sdm_ctx* c)
-{
-    sdm_ctx::Vmap& v = c->vmap;
-    (void)hipFree(v.d_table);
-    (void)hipFree(v.d_rec);
-    (void)hipFree(v.d_evid);
-    (void)hipFree(v.d_scratch);
-    (void)hipFree(v.d_out);
-    (void)hipHostFree(v.h_pin);
-    (void)hipFree(v.obs.d_table);
-    (void)hipFree(v.obs.d_log);
-    (void)hipFree(v.obs.d_ent);
-    (void)hipFree(v.obs.d_scratch);
-    (void)hipFree(v.obs.d_out);
-    (void)hipHostFree(v.obs.h_pin);
-    (void)hipFree(v.cls.d_pub);
-    v = sdm_ctx::Vmap{};
-}
-
-int sdm_vmap_open(sdm_ctx* c, float voxel_size, long long reserve_voxels)
-{
-    if (!c) return fail(SDM_EINVAL, "null argument");
-    if (c->vmap.open) return fail(SDM_ESTATE, "the context already has an open voxel map");
-    if (!c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
-    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(SDM_EINVAL, "voxel_size must be finite and > 0");
-    const float inv = 1.0f / voxel_size;
-    if (!std::isfinite(inv)) return fail(SDM_EINVAL, "1 / voxel_size is not finite");
-    if (reserve_voxels < 0 || reserve_voxels > (1ll << 30)) return fail(SDM_EINVAL, "reserve_voxels outside 0 .. 2^30");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    sdm_ctx::Vmap& v = c->vmap;
-    unsigned long long cap = 1024;
-    while (cap < 2ull * (unsigned long long)reserve_voxels) cap <<= 1;
-    int rc;
-    if ((rc = vmap_make_table(c, cap, &v.d_table, &v.tb)) || (rc = vmap_make_records(reserve_voxels, &v.d_rec, &v.rec))) {
-        vmap_free(c);
-        return rc;
-    }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        vmap_free(c);
-        return fail(SDM_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    }
-    v.cap = cap;
-    v.rec_cap = std::max(reserve_voxels, 1ll);
-    v.voxel_size = voxel_size;
-    v.inv = inv;
-    v.open = true;
-    return SDM_OK;
-}
-
-int sdm_vmap_clear(sdm_ctx* c)
-{
-    if (!c) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
-    HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
-    if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, 2 * ext_align(8 * (size_t)v.rec_cap), c->stream));
-    if (v.obs.d_table) HIP_TRY(hipMemsetAsync(v.obs.d_table, 0xff, 20 * (size_t)v.obs.cap, c->stream));
-    if (v.obs.d_ent) {  // (the log keeps its capacity; its content is dead with E = 0)
-        const size_t b4 = ext_align(4 * (size_t)v.rec_cap);
-        HIP_TRY(hipMemsetAsync(v.obs.d_ent, 0xff, b4, c->stream));
-        HIP_TRY(hipMemsetAsync(v.obs.d_ent + b4, 0, b4, c->stream));
-    }
-    if (v.cls.d_pub) HIP_TRY(hipMemsetAsync(v.cls.d_pub, 0, (size_t)v.rec_cap, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    v.cls.published = v.cls.calls = 0;
-    v.M = v.points = v.dropped = v.calls = v.rehashes = 0;
-    v.obs.E = v.obs.calls = v.obs.rehashes = 0;
-    v.obs.seen.clear();
-    return SDM_OK;
-}
-
-int sdm_vmap_close(sdm_ctx* c)
-{
-    if (!c) return fail(SDM_EINVAL, "null argument");
-    if (!c->vmap.open) return fail(SDM_ESTATE, "no open voxel map");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    vmap_free(c);
-    return SDM_OK;
-}
-
-int sdm_vmap_get_info(sdm_ctx* c, sdm_vmap_info* info)
-{
-    if (!c || !info) return fail(SDM_EINVAL, "null argument");
-    const sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    std::memset(info, 0, sizeof(*info));
-    info->voxels = v.M;
-    info->points = v.points;
-    info->dropped = v.dropped;
-    info->calls = v.calls;
-    info->table_slots = (long long)v.cap;
-    info->rehashes = v.rehashes;
-    info->voxel_size = v.voxel_size;
-    return SDM_OK;
-}
-
-// table and records for `need` entries, made before anything is inserted; the old ones stay intact if an allocation fails
-static int vmap_grow(sdm_ctx* c, long long need)
-{
-    sdm_ctx::Vmap& v = c->vmap;
-    int rc;
-    if (2ull * (unsigned long long)need > v.cap) {
-        unsigned long long cap = v.cap;
-        while (cap < 2ull * (unsigned long long)need) cap <<= 1;
-        unsigned char* block = nullptr;
-        VmapTable nw{};
-        if ((rc = vmap_make_table(c, cap, &block, &nw))) return rc;
-        HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 8, c->stream));  // (the counters: the caller has sized the scratch)
-        const unsigned long long per = 1ull << 31;  // work-items of one dispatch
-        for (unsigned long long h0 = 0; h0 < v.cap; h0 += per)
-            hipLaunchKernelGGL(k_vmap_rehash, dim3((unsigned)((std::min(per, v.cap - h0) + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-                               c->stream, v.tb.keys, v.tb.id, v.cap, h0, nw, reinterpret_cast<unsigned*>(v.d_scratch));
-        unsigned* h_ctr = reinterpret_cast<unsigned*>(v.h_pin);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_ctr, v.d_scratch, 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess || h_ctr[1]) {
-            (void)hipFree(block);
-            return fail(SDM_EHIP, e != hipSuccess ? std::string("voxel map rehash: ") + hipGetErrorString(e)
-                                                  : std::string("voxel map table overflow while rehashing"));
-        }
-        (void)hipFree(v.d_table);
-        v.d_table = block;
-        v.tb = nw;
-        v.cap = cap;
-        v.rehashes++;
-    }
-    if (need > v.rec_cap) {
-        const long long cap = std::max(need, 2 * v.rec_cap);  // geometric: the copies amortise
-        unsigned char* block = nullptr;
-        VmapRecords nr{};
-        if ((rc = vmap_make_records(cap, &block, &nr))) return rc;
-        unsigned char* evid = nullptr;  // the free-space counters grow with the records: M entries copied, the rest zero
-        unsigned long long *ncr = nullptr, *nen = nullptr;
-        if (v.d_evid && (rc = vmap_make_evidence(c, cap, &evid, &ncr, &nen))) {
-            (void)hipFree(block);
-            return rc;
-        }
-        unsigned char* ent = nullptr;  // so do the observations' heads and lengths: M entries copied, the rest empty
-        unsigned *nlast = nullptr, *nncam = nullptr;
-        if (v.obs.d_ent && (rc = vmap_make_obs_entries(c, cap, &ent, &nlast, &nncam))) {
-            (void)hipFree(block);
-            (void)hipFree(evid);
-            return rc;
-        }
-        unsigned char* pub = nullptr;  // and the published flags: M entries copied, the rest 0
-        if (v.cls.d_pub && (rc = vmap_make_published(c, cap, &pub))) {
-            (void)hipFree(block);
-            (void)hipFree(evid);
-            (void)hipFree(ent);
-            return rc;
-        }
-        const size_t m = (size_t)v.M;
-        hipError_t e = hipSuccess;
-        if (pub) {
-            if (m) e = hipMemcpyAsync(pub, v.cls.d_pub, m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
-        }
-        if (ent && e == hipSuccess) {
-            if (m) e = hipMemcpyAsync(nlast, v.obs.last_obs, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (m && e == hipSuccess) e = hipMemcpyAsync(nncam, v.obs.ncam, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
-        }
-        if (evid && e == hipSuccess) {
-            if (m) e = hipMemcpyAsync(ncr, v.crossings, 8 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (m && e == hipSuccess) e = hipMemcpyAsync(nen, v.ends, 8 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess && !m) e = hipStreamSynchronize(c->stream);  // (with m the records' wait below serves)
-        }
-        if (m && e == hipSuccess) {
-            e = hipMemcpyAsync(nr.xyz, v.rec.xyz, 12 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nr.rho_sigma, v.rec.rho_sigma, 8 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nr.pixel, v.rec.pixel, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nr.tag, v.rec.tag, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nr.multiplicity, v.rec.multiplicity, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nr.epoch, v.rec.epoch, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nr.intensity, v.rec.intensity, m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(block);
-            (void)hipFree(evid);
-            (void)hipFree(ent);
-            (void)hipFree(pub);
-            return fail(SDM_EHIP, std::string("voxel map records: ") + hipGetErrorString(e));
-        }
-        if (pub) {  // (waited for above, as the records are)
-            (void)hipFree(v.cls.d_pub);
-            v.cls.d_pub = pub;
-        }
-        if (ent) {  // (waited for above, as the records are)
-            (void)hipFree(v.obs.d_ent);
-            v.obs.d_ent = ent;
-            v.obs.last_obs = nlast;
-            v.obs.ncam = nncam;
-        }
-        if (evid) {  // (waited for above, as the records are)
-            (void)hipFree(v.d_evid);
-            v.d_evid = evid;
-            v.crossings = ncr;
-            v.ends = nen;
-        }
-        (void)hipFree(v.d_rec);
-        v.d_rec = block;
-        v.rec = nr;
-        v.rec_cap = cap;
-    }
-    return SDM_OK;
-}
-
-int sdm_vmap_integrate(sdm_ctx* c, int n, const int* slots, const int* tags, int source, double max_sigma, double min_rho,
-                       sdm_vmap_delta* delta)
-{
-    if (delta) delta->plain_total = delta->dropped = delta->first_created = delta->created = delta->updated = 0;
-    if (!c) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
-    unsigned* upd_dst = delta ? delta->updated_ids : nullptr;
-    if (upd_dst && delta->updated_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
-    if (upd_dst && delta->on_device && (uintptr_t)upd_dst % 4) return fail(SDM_EINVAL, "device buffer not aligned (updated_ids: 4 B)");
-
-    // the plain cloud, all four fields, into the engine's staging
-    ExtractStaged st{};
-    st.pixel = st.intensity = true;
-    sdm_point_buffers none{};
-    std::vector<long long> plain((size_t)n + 1, 0);
-    int rc = extract_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
-    if (rc) return rc;
-    const long long T = st.total;
-    if (delta) delta->plain_total = T, delta->first_created = v.M;
-    if (v.M + T > (1ll << 30)) return fail(SDM_EINVAL, "more than 2^30 entries and plain points: the voxel map's table would exceed 2^31 slots");
-    if (upd_dst && delta->updated_capacity < std::min(v.M, T))
-        return fail(SDM_EINVAL, "updated_capacity " + std::to_string(delta->updated_capacity) + " < min(entries, plain points) = " +
-                                    std::to_string(std::min(v.M, T)) + " (plain_total and first_created filled)");
-    if (T == 0) {  // (extract_core has waited for the stream)
-        v.calls++;
-        return SDM_OK;
-    }
-
-    // scratch, staging and growth: everything is allocated before anything is inserted
-    const long long vt = (T + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t where_b = ext_align(4 * (size_t)T), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
-    const size_t blk_b = ext_align(8 * (size_t)vb), tag_b = ext_align(4 * (size_t)n);
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + where_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b + tag_b))) return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tag_b))) return rc;
-    const bool stage_upd = upd_dst && !delta->on_device;
-    if (stage_upd && (rc = ext_grow_dev(&v.d_out, &v.out_bytes, 4 * (size_t)std::min(v.M, T)))) return rc;
-    if ((rc = vmap_grow(c, v.M + T))) return rc;
-    unsigned char* p = v.d_scratch;
-    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                           // {dropped, overflow}
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, updated, dropped, overflow}
-    p += 512;
-    unsigned* d_where = reinterpret_cast<unsigned*>(p);
-    p += where_b;
-    unsigned* d_cnt_new = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_cnt_upd = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off_new = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned* d_off_upd = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum_new = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_new = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_bsum_upd = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_upd = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    int* d_tags = reinterpret_cast<int*>(p);
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
-    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
-    for (int i = 0; i < n; i++) h_tags[i] = tags ? tags[i] : slots[i];
-
-    HIP_TRY(hipMemsetAsync(d_ctr, 0, 8, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_tags, h_tags, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long pblocks = (T + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vmap_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, st.at.xyz,
-                           st.at.rho_sigma, T, b0 * BLOCK, v.inv, v.tb, d_where, d_ctr);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where, T,
-                           t0, d_cnt_new, d_cnt_upd);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_new, vt, d_off_new, d_bsum_new);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_new, (int)vb, d_boff_new);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_upd, vt, d_off_upd, d_bsum_upd);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_upd, (int)vb, d_boff_upd);
-    hipLaunchKernelGGL(k_vmap_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_new, d_boff_new, d_off_upd, d_boff_upd, d_ctr,
-                       d_tot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: created and updated
-    if (h_tot[3]) return fail(SDM_EHIP, "voxel map table overflow");
-    const long long created = (long long)h_tot[0], updated = (long long)h_tot[1], dropped = (long long)h_tot[2];
-
-    unsigned* d_upd = !upd_dst ? nullptr : stage_upd ? reinterpret_cast<unsigned*>(v.d_out) : upd_dst;
-    const unsigned first_created = (unsigned)v.M, epoch = (unsigned)(v.calls + 1);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_ids, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
-                           first_created, T, t0, d_off_new, d_boff_new);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
-                           first_created, epoch, T, t0, d_off_upd, d_boff_upd, st.at, st.d_offsets, d_tags, n, d_upd);
-    HIP_TRY(hipGetLastError());
-    if (stage_upd && updated)
-        HIP_TRY(hipMemcpyAsync(upd_dst, d_upd, 4 * (size_t)updated, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    v.M += created;
-    v.points += T - dropped;
-    v.dropped += dropped;
-    v.calls++;
-    if (delta) delta->created = created, delta->updated = updated, delta->dropped = dropped;
-    return SDM_OK;
-}
-
-int sdm_vmap_fetch(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_point_buffers* out,
-                   sdm_vmap_fields* extra)
-{
-    if (!c || !out) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    int* tag = extra ? extra->tag : nullptr;
-    unsigned* mult = extra ? extra->multiplicity : nullptr;
-    unsigned* epoch = extra ? extra->epoch : nullptr;
-    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity && !tag && !mult && !epoch)
-        return fail(SDM_EINVAL, "no output requested");
-    if (count < 0 || out->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
-    if (count > out->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
-    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
-        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
-    const bool dev = out->on_device != 0;
-    if (dev && (((uintptr_t)out->xyz | (uintptr_t)out->pixel | (uintptr_t)tag | (uintptr_t)mult | (uintptr_t)epoch | (uintptr_t)ids) % 4 ||
-                (uintptr_t)out->rho_sigma % 8))
-        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel, tag, multiplicity, epoch, ids: 4 B; rho_sigma: 8 B)");
-    if (ids && !dev)
-        for (long long j = 0; j < count; j++)
-            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (count == 0) return SDM_OK;
-    const size_t m = (size_t)count;
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    VmapRecords src = v.rec;
-    unsigned* h_bad = nullptr;
-    if (!ids) {
-        const size_t f = (size_t)first;
-        src.xyz += 3 * f, src.pixel += f, src.rho_sigma += f, src.intensity += f, src.tag += f, src.multiplicity += f, src.epoch += f;
-    } else {
-        // ids, the flag and -- for host destinations -- one dense region per requested field
-        size_t at = ext_align(4 * m) + 256;
-        size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, tag_off = 0, mult_off = 0, ep_off = 0;
-        if (!dev) {
-            if (out->xyz) xyz_off = at, at += ext_align(12 * m);
-            if (out->pixel) pix_off = at, at += ext_align(4 * m);
-            if (out->rho_sigma) rs_off = at, at += ext_align(8 * m);
-            if (out->intensity) im_off = at, at += ext_align(m);
-            if (tag) tag_off = at, at += ext_align(4 * m);
-            if (mult) mult_off = at, at += ext_align(4 * m);
-            if (epoch) ep_off = at, at += ext_align(4 * m);
-        }
-        int rc;
-        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, at)) || (rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256))) return rc;
-        unsigned char* b = v.d_out;
-        const unsigned* d_ids = ids;
-        unsigned* d_bad = reinterpret_cast<unsigned*>(b + ext_align(4 * m));
-        h_bad = reinterpret_cast<unsigned*>(v.h_pin);
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(b, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
-            d_ids = reinterpret_cast<const unsigned*>(b);
-        }
-        VmapRecords dst{};
-        if (dev) {
-            dst.xyz = out->xyz, dst.pixel = out->pixel, dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
-            dst.intensity = out->intensity, dst.tag = tag, dst.multiplicity = mult, dst.epoch = epoch;
-        } else {
-            dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
-            dst.pixel = out->pixel ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
-            dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
-            dst.intensity = out->intensity ? b + im_off : nullptr;
-            dst.tag = tag ? reinterpret_cast<int*>(b + tag_off) : nullptr;
-            dst.multiplicity = mult ? reinterpret_cast<unsigned*>(b + mult_off) : nullptr;
-            dst.epoch = epoch ? reinterpret_cast<unsigned*>(b + ep_off) : nullptr;
-        }
-        HIP_TRY(hipMemsetAsync(d_bad, 0, 4, c->stream));
-        const long long per = (1ll << 31) / BLOCK;
-        const long long blocks = (count + BLOCK - 1) / BLOCK;
-        for (long long b0 = 0; b0 < blocks; b0 += per)
-            hipLaunchKernelGGL(k_vmap_gather, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, v.rec, d_ids,
-                               count, b0 * BLOCK, (unsigned)v.M, dst, d_bad);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-        src = dst;
-    }
-    if (!ids || !dev) {  // one copy per field of exactly count elements
-        if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, src.xyz, 12 * m, kind, c->stream));
-        if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, src.pixel, 4 * m, kind, c->stream));
-        if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, src.rho_sigma, 8 * m, kind, c->stream));
-        if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, src.intensity, m, kind, c->stream));
-        if (tag) HIP_TRY(hipMemcpyAsync(tag, src.tag, 4 * m, kind, c->stream));
-        if (mult) HIP_TRY(hipMemcpyAsync(mult, src.multiplicity, 4 * m, kind, c->stream));
-        if (epoch) HIP_TRY(hipMemcpyAsync(epoch, src.epoch, 4 * m, kind, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
-    return SDM_OK;
-}
-
-// ---- free-space evidence on the persistent voxel map (sdm_vmap_carve.h) --------------------------------------------------
-int sdm_vmap_carve(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
-                   double min_rho, sdm_vmap_carve_args* cv)
-{
-    if (cv) cv->plain_total = cv->rays_total = cv->rays_skipped = cv->cells_visited = cv->cells_hit = cv->ends_hit = 0;
-    if (!c || !cv) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
-    if (cv->end_margin < 0) return fail(SDM_EINVAL, "negative end_margin");
-    if (cv->max_steps < 1 || cv->max_steps > SDM_FREESPACE_MAX_STEPS)
-        return fail(SDM_EINVAL, "max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS");
-    if (n_nbr < 0) return fail(SDM_EINVAL, "negative n_nbr");
-    if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
-    if ((n_nbr == 0) != (nbr_slots == nullptr))
-        return fail(SDM_EINVAL, n_nbr ? "null nbr_slots" : "n_nbr == 0 with a neighbour table");
-
-    // the plain cloud (xyz and rho_sigma) and, with neighbours, the support words into the engine's staging
-    ExtractStaged st{};
-    st.support = n_nbr > 0;
-    sdm_point_buffers none{};
-    std::vector<long long> plain((size_t)n + 1, 0);
-    int rc = extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
-    if (rc) return rc;
-    const long long T = st.total;
-    cv->plain_total = T;
-    if (T == 0) return SDM_OK;  // (extract_core has waited for the stream)
-
-    // the cameras of the call: its distinct slots in ascending order, and per slot i the distinct neighbours other than
-    // slots[i], in the order of their first column, each with the mask of the columns that name it (extract_core has
-    // checked every slot's range; n_nbr <= 64)
-    std::vector<int> cam_of((size_t)c->cfg.max_keyframes, -1);
-    for (int i = 0; i < n; i++) cam_of[(size_t)slots[i]] = 0;
-    for (size_t i = 0; i < (size_t)n * (size_t)n_nbr; i++) cam_of[(size_t)nbr_slots[i]] = 0;
-    int Cn = 0;
-    std::vector<int> slot_of_cam;
-    for (int s = 0; s < c->cfg.max_keyframes; s++)
-        if (cam_of[(size_t)s] == 0) cam_of[(size_t)s] = Cn++, slot_of_cam.push_back(s);
-    std::vector<std::vector<std::pair<int, unsigned long long>>> lists((size_t)n);
-    int D = 0;
-    for (int i = 0; i < n; i++) {
-        auto& l = lists[(size_t)i];
-        for (int j = 0; j < n_nbr; j++) {
-            const int s = nbr_slots[(size_t)i * (size_t)n_nbr + (size_t)j];
-            if (s == slots[i]) continue;
-            size_t k = 0;
-            while (k < l.size() && l[k].first != s) k++;
-            if (k == l.size()) l.emplace_back(s, 0ull);
-            l[k].second |= 1ull << j;
-        }
-        D = std::max(D, (int)l.size());
-    }
-
-    // the counters, the scratch and the pinned mirror: everything is allocated before anything is counted
-    if (!v.d_evid && (rc = vmap_make_evidence(c, v.rec_cap, &v.d_evid, &v.crossings, &v.ends))) return rc;
-    const size_t nd = (size_t)n * (size_t)D;
-    const size_t org_b = ext_align(16 * (size_t)Cn), own_b = ext_align(4 * (size_t)n), cam_b = ext_align(4 * nd),
-                 mask_b = ext_align(8 * nd), tab_b = org_b + own_b + cam_b + mask_b;
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + tab_b))) return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tab_b))) return rc;
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(v.d_scratch + 256);
-    unsigned char* d_tab = v.d_scratch + 512;
-    unsigned char* h_tab = v.h_pin + 256;
-    float* h_org = reinterpret_cast<float*>(h_tab);
-    int* h_own = reinterpret_cast<int*>(h_tab + org_b);
-    int* h_cam = reinterpret_cast<int*>(h_tab + org_b + own_b);
-    unsigned long long* h_mask = reinterpret_cast<unsigned long long*>(h_tab + org_b + own_b + cam_b);
-    for (int q = 0; q < Cn; q++) {  // the camera centres from the current poses, as pointset_pixel forms Ow: O = -(Rwc * tcw)
-        const float* Tcw = c->h_meta[slot_of_cam[(size_t)q]].Tcw;
-        float Rwc[9], Ow[3];
-        const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
-        for (int i = 0; i < 3; i++)
-            for (int k = 0; k < 3; k++) Rwc[i * 3 + k] = Tcw[k * 4 + i];
-        mat3_vec(Rwc, tcw, Ow);
-        for (int i = 0; i < 3; i++) h_org[q * 4 + i] = -Ow[i];
-        h_org[q * 4 + 3] = 0.f;
-    }
-    for (int i = 0; i < n; i++) {
-        h_own[i] = cam_of[(size_t)slots[i]];
-        const auto& l = lists[(size_t)i];
-        for (int d = 0; d < D; d++) {
-            const bool have = (size_t)d < l.size();
-            h_cam[(size_t)i * (size_t)D + (size_t)d] = have ? cam_of[(size_t)l[(size_t)d].first] : 0;
-            h_mask[(size_t)i * (size_t)D + (size_t)d] = have ? l[(size_t)d].second : 0ull;
-        }
-    }
-    HIP_TRY(hipMemsetAsync(d_tot, 0, 64, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_b, hipMemcpyHostToDevice, c->stream));
-    VmapCarveIn in;
-    in.xyz = st.at.xyz;
-    in.support = D ? st.d_support : nullptr;
-    in.plain_offsets = st.d_offsets;
-    in.origin = reinterpret_cast<const float*>(d_tab);
-    in.own_cam = reinterpret_cast<const int*>(d_tab + org_b);
-    in.nbr_cam = reinterpret_cast<const int*>(d_tab + org_b + own_b);
-    in.nbr_mask = reinterpret_cast<const unsigned long long*>(d_tab + org_b + own_b + cam_b);
-    in.T = T;
-    in.n = n;
-    in.D = D;
-    in.M = (unsigned)v.M;
-    in.voxel = v.voxel_size;
-    in.inv = v.inv;
-    in.end_margin = cv->end_margin;
-    in.max_steps = cv->max_steps;
-    const long long E = ((long long)D + 1) * T;  // candidates, camera-major
-    const long long per = (1ll << 31) / BLOCK;   // workgroups of one dispatch (for_ref_slices)
-    const long long eblocks = (E + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < eblocks; b0 += per)
-        hipLaunchKernelGGL(k_vmap_carve, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, E,
-                           v.tb, v.crossings, v.ends, d_tot);
-    HIP_TRY(hipGetLastError());
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end, with the totals
-    cv->rays_total = (long long)h_tot[0];
-    cv->rays_skipped = (long long)h_tot[1];
-    cv->cells_visited = (long long)h_tot[2];
-    cv->cells_hit = (long long)h_tot[3];
-    cv->ends_hit = (long long)h_tot[4];
-    return SDM_OK;
-}
-
-int sdm_vmap_fetch_evidence(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_vmap_evidence* ev)
-{
-    if (!c || !ev) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (!ev->crossings && !ev->ends) return fail(SDM_EINVAL, "no output requested");
-    if (count < 0 || ev->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
-    if (count > ev->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
-    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
-        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
-    const bool dev = ev->on_device != 0;
-    if (dev && (((uintptr_t)ev->crossings | (uintptr_t)ev->ends) % 8 || (uintptr_t)ids % 4))
-        return fail(SDM_EINVAL, "device buffer not aligned (crossings, ends: 8 B; ids: 4 B)");
-    if (ids && !dev)
-        for (long long j = 0; j < count; j++)
-            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (count == 0) return SDM_OK;
-    const size_t m = (size_t)count;
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const unsigned long long *src_cr = v.crossings, *src_en = v.ends;  // (null: no carve has run, every counter reads 0)
-    unsigned* h_bad = nullptr;
-    if (!ids) {
-        if (src_cr) src_cr += first, src_en += first;
-    } else {
-        // ids, the flag and -- for host destinations -- one dense region per requested counter
-        const size_t ids_b = ext_align(4 * m), b8 = ext_align(8 * m);
-        int rc;
-        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, ids_b + 256 + (dev ? 0 : 2 * b8))) ||
-            (rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256)))
-            return rc;
-        unsigned char* b = v.d_out;
-        const unsigned* d_ids = ids;
-        unsigned* d_bad = reinterpret_cast<unsigned*>(b + ids_b);
-        h_bad = reinterpret_cast<unsigned*>(v.h_pin);
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(b, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
-            d_ids = reinterpret_cast<const unsigned*>(b);
-        }
-        unsigned long long* dst_cr = dev ? ev->crossings : ev->crossings ? reinterpret_cast<unsigned long long*>(b + ids_b + 256) : nullptr;
-        unsigned long long* dst_en = dev ? ev->ends : ev->ends ? reinterpret_cast<unsigned long long*>(b + ids_b + 256 + b8) : nullptr;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, 4, c->stream));
-        const long long per = (1ll << 31) / BLOCK;
-        const long long blocks = (count + BLOCK - 1) / BLOCK;
-        for (long long b0 = 0; b0 < blocks; b0 += per)
-            hipLaunchKernelGGL(k_vmap_evidence, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, src_cr, src_en,
-                               d_ids, count, b0 * BLOCK, (unsigned)v.M, dst_cr, dst_en, d_bad);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-        src_cr = dst_cr, src_en = dst_en;
-    }
-    if (!ids || !dev) {  // one copy per counter of exactly count elements (zeros before the first carve)
-        unsigned long long* dst[2] = {ev->crossings, ev->ends};
-        const unsigned long long* src[2] = {src_cr, src_en};
-        for (int k = 0; k < 2; k++) {
-            if (!dst[k]) continue;
-            if (src[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], 8 * m, kind, c->stream));
-            else if (dev) HIP_TRY(hipMemsetAsync(dst[k], 0, 8 * m, c->stream));
-            else std::memset(dst[k], 0, 8 * m);
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
-    return SDM_OK;
-}
-
-// ---- camera lists on the persistent voxel map: the observation log (sdm_vmap_obs.h) --------------------------------------
-// one block for the set: keys | ord | idx (20 B per slot), all ones: empty keys, ord's identity, no index
-static int vobs_make_table(sdm_ctx* c, unsigned long long cap, unsigned char** block, VobsTable* tb)
-{
-    const size_t n = (size_t)cap;
-    HIP_TRY(hipMalloc((void**)block, 20 * n));
-    unsigned char* p = *block;
-    tb->keys = reinterpret_cast<unsigned long long*>(p);
-    tb->ord = reinterpret_cast<unsigned long long*>(p + 8 * n);
-    tb->idx = reinterpret_cast<unsigned*>(p + 16 * n);
-    tb->mask = cap - 1;
-    const hipError_t e = hipMemsetAsync(p, 0xff, 20 * n, c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(*block);
-        *block = nullptr;
-        return fail(SDM_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
-    }
-    return SDM_OK;
-}
-
-// set, log and per-entry arrays for `need` observations, made before anything is inserted; the old ones stay intact if
-// an allocation fails
-static int vobs_grow(sdm_ctx* c, long long need)
-{
-    sdm_ctx::Vmap& v = c->vmap;
-    sdm_ctx::Vmap::Obs& o = v.obs;
-    int rc;
-    if (!o.d_ent && (rc = vmap_make_obs_entries(c, v.rec_cap, &o.d_ent, &o.last_obs, &o.ncam))) return rc;
-    if (!o.d_table || 2ull * (unsigned long long)need > o.cap) {
-        unsigned long long cap = std::max(o.cap, 1024ull);
-        while (cap < 2ull * (unsigned long long)need) cap <<= 1;
-        unsigned char* block = nullptr;
-        VobsTable nw{};
-        if ((rc = vobs_make_table(c, cap, &block, &nw))) return rc;
-        if (o.d_table) {
-            unsigned* d_flag = reinterpret_cast<unsigned*>(o.d_scratch);  // (the caller has sized the scratch)
-            unsigned* h_flag = reinterpret_cast<unsigned*>(o.h_pin);
-            hipError_t e = hipMemsetAsync(d_flag, 0, 4, c->stream);
-            const unsigned long long per = 1ull << 31;  // work-items of one dispatch
-            for (unsigned long long h0 = 0; h0 < o.cap && e == hipSuccess; h0 += per)
-                hipLaunchKernelGGL(k_vobs_rehash, dim3((unsigned)((std::min(per, o.cap - h0) + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-                                   c->stream, o.tb.keys, o.tb.idx, o.cap, h0, nw, d_flag);
-            if (e == hipSuccess) e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess || *h_flag) {
-                (void)hipFree(block);
-                return fail(SDM_EHIP, e != hipSuccess ? std::string("observation set rehash: ") + hipGetErrorString(e)
-                                                      : std::string("observation set overflow while rehashing"));
-            }
-            (void)hipFree(o.d_table);  // (only after the wait)
-            o.rehashes++;
-        }
-        o.d_table = block;
-        o.tb = nw;
-        o.cap = cap;
-    }
-    if (need > o.log_cap) {
-        const long long cap = std::max(need, 2 * o.log_cap);  // geometric: the copies amortise
-        const size_t b4 = ext_align(4 * (size_t)cap);
-        unsigned char* block = nullptr;
-        HIP_TRY(hipMalloc((void**)&block, 3 * b4));
-        VobsLog nl;
-        nl.entry = reinterpret_cast<unsigned*>(block);
-        nl.tag = reinterpret_cast<int*>(block + b4);
-        nl.prev = reinterpret_cast<unsigned*>(block + 2 * b4);
-        const size_t m = (size_t)o.E;
-        hipError_t e = hipSuccess;
-        if (m) {
-            e = hipMemcpyAsync(nl.entry, o.log.entry, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nl.tag, o.log.tag, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(nl.prev, o.log.prev, 4 * m, hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(block);
-            return fail(SDM_EHIP, std::string("observation log: ") + hipGetErrorString(e));
-        }
-        (void)hipFree(o.d_log);
-        o.d_log = block;
-        o.log = nl;
-        o.log_cap = cap;
-    }
-    return SDM_OK;
-}
-
-int sdm_vmap_observe(sdm_ctx* c, int n, const int* slots, const int* tags, int n_nbr, const int* nbr_slots, const int* nbr_tags,
-                     int source, double max_sigma, double min_rho, sdm_vmap_observe_delta* ob)
-{
-    if (ob) ob->plain_total = ob->unmapped = ob->candidates = ob->first_created = ob->created = 0;
-    if (!c || !ob) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    sdm_ctx::Vmap::Obs& o = v.obs;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (n < 0 || (n > 0 && !slots)) return fail(SDM_EINVAL, "null or negative slot list");
-    if (n_nbr < 0) return fail(SDM_EINVAL, "negative n_nbr");
-    if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
-    if ((n_nbr == 0) != (nbr_slots == nullptr))
-        return fail(SDM_EINVAL, n_nbr ? "null nbr_slots" : "n_nbr == 0 with a neighbour table");
-    if (nbr_tags && !nbr_slots) return fail(SDM_EINVAL, "nbr_tags without nbr_slots");
-    const size_t nn = (size_t)n * (size_t)n_nbr;
-    if (tags)
-        for (int i = 0; i < n; i++)
-            if (tags[i] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
-    if (nbr_tags)
-        for (size_t i = 0; i < nn; i++)
-            if (nbr_tags[i] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
-
-    // the plain cloud (xyz and rho_sigma) and, with neighbours, the support words into the engine's staging
-    ExtractStaged st{};
-    st.support = n_nbr > 0;
-    sdm_point_buffers none{};
-    std::vector<long long> plain((size_t)n + 1, 0);
-    int rc = extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, &none, nullptr, plain.data(), &st);
-    if (rc) return rc;
-    const long long T = st.total;
-    ob->plain_total = T;
-
-    // per row the ascending list of its distinct tags with the columns that name each; the own tag's position is always
-    // live (extract_core has checked every slot's range, so a slot number is a valid tag; n_nbr <= 64)
-    std::vector<std::vector<std::pair<int, unsigned long long>>> lists((size_t)n);
-    std::vector<int> own((size_t)n, 0);
-    int Lmax = 1;
-    long long B = 0;
-    for (int i = 0; i < n; i++) {
-        auto& l = lists[(size_t)i];
-        const int mine = tags ? tags[i] : slots[i];
-        l.emplace_back(mine, 0ull);
-        for (int j = 0; j < n_nbr; j++) {
-            const size_t at = (size_t)i * (size_t)n_nbr + (size_t)j;
-            const int t = nbr_tags ? nbr_tags[at] : nbr_slots[at];
-            size_t k = 0;
-            while (k < l.size() && l[k].first != t) k++;
-            if (k == l.size()) l.emplace_back(t, 0ull);
-            l[k].second |= 1ull << j;
-        }
-        std::sort(l.begin(), l.end());  // (the tags are distinct: the masks never decide)
-        for (size_t k = 0; k < l.size(); k++)
-            if (l[k].first == mine) own[(size_t)i] = (int)k;
-        Lmax = std::max(Lmax, (int)l.size());
-        B += (plain[(size_t)i + 1] - plain[(size_t)i]) * (long long)l.size();
-    }
-    if (o.E + B > (1ll << 30))
-        return fail(SDM_EINVAL, "more than 2^30 observations and candidates: the observation set would exceed 2^31 slots");
-    const long long Ec = T * (long long)Lmax;  // candidates, point-major
-    if (Ec > (1ll << 40)) return fail(SDM_EINVAL, "more than 2^40 candidates (plain points x the longest row) in one call");
-    if (T == 0) {  // (extract_core has waited for the stream)
-        ob->first_created = o.E;
-        o.calls++;
-        return SDM_OK;
-    }
-
-    // scratch, pinned mirror and growth: everything is allocated before anything is inserted
-    const long long vt = (Ec + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t nl = (size_t)n * (size_t)Lmax;
-    const size_t where_b = ext_align(4 * (size_t)Ec), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1)),
-                 blk_b = ext_align(8 * (size_t)vb);
-    const size_t tag_b = ext_align(4 * nl), mask_b = ext_align(8 * nl), own_b = ext_align(4 * (size_t)n), tab_b = mask_b + tag_b + own_b;
-    if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, 512 + where_b + tcnt_b + toff_b + 2 * blk_b + tab_b))) return rc;
-    if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256 + tab_b))) return rc;
-    if ((rc = vobs_grow(c, o.E + B))) return rc;
-    unsigned char* p = o.d_scratch;
-    unsigned long long* d_ctr = reinterpret_cast<unsigned long long*>(p + 64);   // {unmapped, candidates, overflow}
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, unmapped, candidates, overflow}
-    p += 512;
-    unsigned* d_where = reinterpret_cast<unsigned*>(p);
-    p += where_b;
-    unsigned* d_cnt = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned char* d_tab = p;
-    unsigned char* h_tab = o.h_pin + 256;
-    unsigned long long* h_mask = reinterpret_cast<unsigned long long*>(h_tab);
-    int* h_tag = reinterpret_cast<int*>(h_tab + mask_b);
-    int* h_own = reinterpret_cast<int*>(h_tab + mask_b + tag_b);
-    for (int i = 0; i < n; i++) {
-        const auto& l = lists[(size_t)i];
-        h_own[i] = own[(size_t)i];
-        for (int d = 0; d < Lmax; d++) {
-            const bool have = (size_t)d < l.size();
-            h_tag[(size_t)i * (size_t)Lmax + (size_t)d] = have ? l[(size_t)d].first : 0;
-            h_mask[(size_t)i * (size_t)Lmax + (size_t)d] = have ? l[(size_t)d].second : 0ull;
-        }
-    }
-    HIP_TRY(hipMemsetAsync(d_ctr, 0, 24, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_b, hipMemcpyHostToDevice, c->stream));
-    VobsIn in;
-    in.xyz = st.at.xyz;
-    in.support = n_nbr > 0 ? st.d_support : nullptr;
-    in.plain_offsets = st.d_offsets;
-    in.row_mask = reinterpret_cast<const unsigned long long*>(d_tab);
-    in.row_tag = reinterpret_cast<const int*>(d_tab + mask_b);
-    in.own = reinterpret_cast<const int*>(d_tab + mask_b + tag_b);
-    in.T = T;
-    in.n = n;
-    in.Lmax = Lmax;
-    in.inv = v.inv;
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long eblocks = (Ec + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < eblocks; b0 += per)
-        hipLaunchKernelGGL(k_vobs_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, Ec,
-                           v.tb, o.tb, d_where, d_ctr);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_where, Ec, t0,
-                           d_cnt);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt, vt, d_off, d_bsum);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)vb, d_boff);
-    hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off, d_boff, d_ctr, d_tot);
-    HIP_TRY(hipGetLastError());
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(o.h_pin);
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: created
-    if (h_tot[3]) return fail(SDM_EHIP, "observation set overflow");
-    const long long created = (long long)h_tot[0];
-    if (created > B) return fail(SDM_EHIP, "observation log: more pairs created than the a-priori bound");
-
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log, o.last_obs,
-                           o.ncam, d_where, (unsigned)o.E, Ec, t0, d_off, d_boff);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (const auto& l : lists)  // the tags seen so far bound every list's length (sdm_vmap_fetch_cameras' scan)
-        for (const auto& tm : l) {
-            const auto it = std::lower_bound(o.seen.begin(), o.seen.end(), tm.first);
-            if (it == o.seen.end() || *it != tm.first) o.seen.insert(it, tm.first);
-        }
-    ob->unmapped = (long long)h_tot[1];
-    ob->candidates = (long long)h_tot[2];
-    ob->first_created = o.E;
-    ob->created = created;
-    o.E += created;
-    o.calls++;
-    return SDM_OK;
-}
-
-int sdm_vmap_get_obs_info(sdm_ctx* c, sdm_vmap_obs_info* info)
-{
-    if (!c || !info) return fail(SDM_EINVAL, "null argument");
-    const sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    std::memset(info, 0, sizeof(*info));
-    info->observations = v.obs.E;
-    info->calls = v.obs.calls;
-    info->table_slots = (long long)v.obs.cap;
-    info->rehashes = v.obs.rehashes;
-    return SDM_OK;
-}
-
-int sdm_vmap_fetch_observations(sdm_ctx* c, long long first, long long count, sdm_vmap_observations* out)
-{
-    if (!c || !out) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (!out->entry && !out->tag) return fail(SDM_EINVAL, "no output requested");
-    if (count < 0 || out->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
-    if (count > out->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
-    if (first < 0 || first > v.obs.E || count > v.obs.E - first) return fail(SDM_EINVAL, "range beyond the log's observations");
-    const bool dev = out->on_device != 0;
-    if (dev && ((uintptr_t)out->entry | (uintptr_t)out->tag) % 4) return fail(SDM_EINVAL, "device buffer not aligned (entry, tag: 4 B)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (count == 0) return SDM_OK;
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out->entry) HIP_TRY(hipMemcpyAsync(out->entry, v.obs.log.entry + first, 4 * (size_t)count, kind, c->stream));
-    if (out->tag) HIP_TRY(hipMemcpyAsync(out->tag, v.obs.log.tag + first, 4 * (size_t)count, kind, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SDM_OK;
-}
-
-int sdm_vmap_fetch_cameras(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_vmap_cameras* cams)
-{
-    if (cams) cams->cam_total = 0;
-    if (!c || !cams) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    sdm_ctx::Vmap::Obs& o = v.obs;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (!cams->cam_offsets && !cams->cam_tags) return fail(SDM_EINVAL, "no camera output requested");
-    if (count < 0 || cams->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
-    if (cams->cam_tags && cams->cam_capacity < 0) return fail(SDM_EINVAL, "negative cam_capacity");
-    if (count > cams->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
-    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
-        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
-    const bool dev = cams->on_device != 0;
-    if (dev && ((uintptr_t)cams->cam_offsets % 8 || ((uintptr_t)cams->cam_tags | (uintptr_t)ids) % 4))
-        return fail(SDM_EINVAL, "device buffer not aligned (cam_offsets: 8 B; cam_tags, ids: 4 B)");
-    if (ids && !dev)
-        for (long long j = 0; j < count; j++)
-            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
-    if ((unsigned long long)std::min(count, (long long)EXT_SCAN) * (unsigned long long)o.seen.size() >= (1ull << 32))
-        return fail(SDM_EINVAL, "min(count, 2048) x (distinct tags observed) >= 2^32: the list pass scans 32-bit sums");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-
-    // ids, lengths, the scan's arrays and -- for host destinations -- the offsets; the tags' staging follows the total
-    const size_t m = (size_t)count;
-    const long long nb = (count + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t ids_b = ext_align(4 * m), len_b = ext_align(4 * m), toff_b = ext_align(4 * (m + 1)), blk_b = ext_align(8 * (size_t)nb),
-                 offs_b = ext_align(8 * (m + 1));
-    const size_t fixed_b = 256 + ids_b + len_b + toff_b + 2 * blk_b + offs_b;
-    int rc;
-    if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, fixed_b)) || (rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
-    unsigned char* p = o.d_scratch;
-    unsigned* d_bad = reinterpret_cast<unsigned*>(p);
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(p + 8);
-    p += 256;
-    unsigned* d_ids_own = reinterpret_cast<unsigned*>(p);
-    p += ids_b;
-    unsigned* d_len = reinterpret_cast<unsigned*>(p);
-    p += len_b;
-    unsigned* d_toff = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    long long* d_offs = dev ? cams->cam_offsets : cams->cam_offsets ? reinterpret_cast<long long*>(p) : nullptr;
-    const unsigned* d_ids = ids;
-    if (ids && !dev && count) {
-        HIP_TRY(hipMemcpyAsync(d_ids_own, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
-        d_ids = d_ids_own;
-    }
-    HIP_TRY(hipMemsetAsync(o.d_scratch, 0, 16, c->stream));
-    const long long per = (1ll << 31) / BLOCK;
-    const long long blocks = (count + BLOCK - 1) / BLOCK, oblocks = (count + 1 + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < blocks; b0 += per)
-        hipLaunchKernelGGL(k_vobs_list_count, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, o.ncam, d_ids, first,
-                           count, b0 * BLOCK, (unsigned)v.M, d_len, d_bad);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)nb), dim3(BLOCK), 0, c->stream, d_len, count, d_toff, d_bsum);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)nb, d_boff);
-    // (the offsets go to a caller's device array only once the total is known to fit: the scan's arrays serve until then)
-    hipLaunchKernelGGL(k_vobs_list_offsets, dim3(1), dim3(BLOCK), 0, c->stream, d_toff, d_boff, count, count, (long long*)nullptr,
-                       d_total);
-    HIP_TRY(hipGetLastError());
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(o.h_pin);
-    HIP_TRY(hipMemcpyAsync(h_tot, o.d_scratch, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: the lists' total
-    if ((unsigned)h_tot[0]) return fail(SDM_EINVAL, "id beyond the map's entries");
-    const long long total = (long long)h_tot[1];
-    cams->cam_total = total;
-    if (cams->cam_tags && total > cams->cam_capacity)
-        return fail(SDM_EINVAL, "cam_capacity " + std::to_string(cams->cam_capacity) + " < " + std::to_string(total) +
-                                    " list entries (cam_total filled)");
-    int* d_tags = cams->cam_tags;
-    if (cams->cam_tags && !dev && total) {
-        if ((rc = ext_grow_dev(&o.d_out, &o.out_bytes, 4 * (size_t)total))) return rc;
-        d_tags = reinterpret_cast<int*>(o.d_out);
-    }
-    if (d_offs)
-        for (long long b0 = 0; b0 < oblocks; b0 += per)
-            hipLaunchKernelGGL(k_vobs_list_offsets, dim3((unsigned)std::min(per, oblocks - b0)), dim3(BLOCK), 0, c->stream, d_toff,
-                               d_boff, count, b0 * BLOCK, d_offs, d_total);
-    if (cams->cam_tags && total)
-        for (long long b0 = 0; b0 < blocks; b0 += per)
-            hipLaunchKernelGGL(k_vobs_list_fill, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, o.log, o.last_obs,
-                               d_ids, first, count, b0 * BLOCK, (unsigned)v.M, d_len, d_toff, d_boff, d_tags);
-    HIP_TRY(hipGetLastError());
-    if (!dev) {
-        if (cams->cam_offsets) HIP_TRY(hipMemcpyAsync(cams->cam_offsets, d_offs, 8 * (m + 1), hipMemcpyDeviceToHost, c->stream));
-        if (cams->cam_tags && total) HIP_TRY(hipMemcpyAsync(cams->cam_tags, d_tags, 4 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SDM_OK;
-}
-
-// ---- classification on the persistent voxel map (sdm_vmap_class.h) --------------------------------------------------------
-int sdm_vmap_classify(sdm_ctx* c, const sdm_vmap_rule* rule, int commit, sdm_vmap_class_delta* delta)
-{
-    if (delta) delta->examined = delta->accepted = delta->retracted = delta->published_total = 0;
-    if (!c || !rule || !delta) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (rule->ratio_den == 0) return fail(SDM_EINVAL, "ratio_den must be at least 1");
-    if (rule->min_neighbours < 0 || rule->min_neighbours > 26) return fail(SDM_EINVAL, "min_neighbours outside 0 .. 26");
-    unsigned* acc_dst = delta->accepted_ids;
-    unsigned* ret_dst = delta->retracted_ids;
-    if ((acc_dst && delta->accepted_capacity < 0) || (ret_dst && delta->retracted_capacity < 0))
-        return fail(SDM_EINVAL, "negative capacity");
-    const bool dev = delta->on_device != 0;
-    if (dev && ((uintptr_t)acc_dst | (uintptr_t)ret_dst) % 4)
-        return fail(SDM_EINVAL, "device buffer not aligned (accepted_ids, retracted_ids: 4 B)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-
-    // the flags, the scratch and the pinned totals: everything but the id staging, which follows the counts
-    const long long M = v.M;
-    const long long vt = (M + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t flag_b = ext_align((size_t)std::max(M, 1ll)), tcnt_b = ext_align(4 * (size_t)std::max(vt, 1ll)),
-                 toff_b = ext_align(4 * (size_t)(vt + 1)), blk_b = ext_align(8 * (size_t)vb);
-    int rc;
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + flag_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b))) return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256))) return rc;
-    if (!v.cls.d_pub && (rc = vmap_make_published(c, v.rec_cap, &v.cls.d_pub))) return rc;
-    delta->examined = M;
-    delta->published_total = v.cls.published;
-    if (M == 0) {  // nothing to examine
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (commit) v.cls.calls++;
-        return SDM_OK;
-    }
-    unsigned char* p = v.d_scratch;
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {accepted, retracted, published_total}
-    p += 512;
-    unsigned char* d_flag = p;
-    p += flag_b;
-    unsigned* d_cnt_acc = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_cnt_ret = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off_acc = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned* d_off_ret = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum_acc = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_acc = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_bsum_ret = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_ret = reinterpret_cast<unsigned long long*>(p);
-
-    VclsRule r;
-    r.min_multiplicity = rule->min_multiplicity;
-    r.min_cameras = rule->min_cameras;
-    r.min_ends = rule->min_ends;
-    r.ratio_num = rule->ratio_num;
-    r.ratio_den = rule->ratio_den;
-    unsigned bits;
-    std::memcpy(&bits, &rule->max_sigma, 4);
-    r.max_sigma_key = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);  // f2key
-    r.min_neighbours = rule->min_neighbours;
-    VclsIn in;
-    in.multiplicity = v.rec.multiplicity;
-    in.rho_sigma = v.rec.rho_sigma;
-    in.ncam = v.obs.ncam;
-    in.crossings = v.crossings;
-    in.ends = v.ends;
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long eblocks = (M + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < eblocks; b0 += per)
-        hipLaunchKernelGGL(k_vcls_local, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream, in, r, M, b0 * BLOCK,
-                           d_flag);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vcls_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec.xyz, v.inv,
-                           r.min_neighbours, M, t0, d_flag, v.cls.d_pub, d_cnt_acc, d_cnt_ret);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_acc, vt, d_off_acc, d_bsum_acc);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_acc, (int)vb, d_boff_acc);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_ret, vt, d_off_ret, d_bsum_ret);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_ret, (int)vb, d_boff_ret);
-    hipLaunchKernelGGL(k_vcls_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_acc, d_boff_acc, d_off_ret, d_boff_ret,
-                       (unsigned long long)v.cls.published, commit, d_tot);
-    HIP_TRY(hipGetLastError());
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 24, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the one wait for the counts
-    const long long accepted = (long long)h_tot[0], retracted = (long long)h_tot[1];
-    delta->accepted = accepted;
-    delta->retracted = retracted;
-    if (acc_dst && accepted > delta->accepted_capacity)
-        return fail(SDM_EINVAL, "accepted_capacity " + std::to_string(delta->accepted_capacity) + " < " + std::to_string(accepted) +
-                                    " accepted entries (the counts are filled)");
-    if (ret_dst && retracted > delta->retracted_capacity)
-        return fail(SDM_EINVAL, "retracted_capacity " + std::to_string(delta->retracted_capacity) + " < " + std::to_string(retracted) +
-                                    " retracted entries (the counts are filled)");
-    const bool list_acc = acc_dst && accepted, list_ret = ret_dst && retracted;
-    if (commit ? accepted + retracted > 0 : (list_acc || list_ret)) {
-        unsigned *d_acc = list_acc ? acc_dst : nullptr, *d_ret = list_ret ? ret_dst : nullptr;
-        const size_t acc_b = list_acc ? ext_align(4 * (size_t)accepted) : 0;
-        if (!dev && (list_acc || list_ret)) {  // (no flag has changed yet: a failure here leaves the state as it was)
-            if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, acc_b + 4 * (size_t)(list_ret ? retracted : 0)))) return rc;
-            if (list_acc) d_acc = reinterpret_cast<unsigned*>(v.d_out);
-            if (list_ret) d_ret = reinterpret_cast<unsigned*>(v.d_out + acc_b);
-        }
-        for (long long t0 = 0; t0 < vt; t0 += per)
-            hipLaunchKernelGGL(k_vcls_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, d_flag, v.cls.d_pub,
-                               commit, M, t0, d_off_acc, d_boff_acc, d_off_ret, d_boff_ret, d_acc, d_ret);
-        HIP_TRY(hipGetLastError());
-        if (!dev) {
-            if (list_acc) HIP_TRY(hipMemcpyAsync(acc_dst, d_acc, 4 * (size_t)accepted, hipMemcpyDeviceToHost, c->stream));
-            if (list_ret) HIP_TRY(hipMemcpyAsync(ret_dst, d_ret, 4 * (size_t)retracted, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (commit) {
-        v.cls.published = (long long)h_tot[2];
-        v.cls.calls++;
-    }
-    delta->published_total = v.cls.published;
-    return SDM_OK;
-}
-
-int sdm_vmap_get_class_info(sdm_ctx* c, sdm_vmap_class_info* info)
-{
-    if (!c || !info) return fail(SDM_EINVAL, "null argument");
-    const sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    std::memset(info, 0, sizeof(*info));
-    info->published = v.cls.published;
-    info->calls = v.cls.calls;
-    return SDM_OK;
-}
-
-int sdm_vmap_fetch_published(sdm_ctx* c, const unsigned* ids, long long first, long long count, sdm_vmap_published* out)
-{
-    if (!c || !out) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (!out->published) return fail(SDM_EINVAL, "no output requested");
-    if (count < 0 || out->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
-    if (count > out->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
-    if (ids ? first != 0 : (first < 0 || first > v.M || count > v.M - first))
-        return fail(SDM_EINVAL, ids ? "first must be 0 with ids" : "range beyond the map's entries");
-    const bool dev = out->on_device != 0;
-    if (dev && (uintptr_t)ids % 4) return fail(SDM_EINVAL, "device buffer not aligned (ids: 4 B)");
-    if (ids && !dev)
-        for (long long j = 0; j < count; j++)
-            if ((long long)ids[j] >= v.M) return fail(SDM_EINVAL, "id beyond the map's entries");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (count == 0) return SDM_OK;
-    const size_t m = (size_t)count;
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const unsigned char* src = v.cls.d_pub;  // (null: no classify has run, every flag reads 0)
-    unsigned* h_bad = nullptr;
-    if (!ids) {
-        if (src) src += first;
-    } else {
-        // ids, the flag and -- for a host destination -- one dense region
-        const size_t ids_b = ext_align(4 * m);
-        int rc;
-        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, ids_b + 256 + (dev ? 0 : ext_align(m)))) ||
-            (rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256)))
-            return rc;
-        unsigned char* b = v.d_out;
-        const unsigned* d_ids = ids;
-        unsigned* d_bad = reinterpret_cast<unsigned*>(b + ids_b);
-        h_bad = reinterpret_cast<unsigned*>(v.h_pin);
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(b, ids, 4 * m, hipMemcpyHostToDevice, c->stream));
-            d_ids = reinterpret_cast<const unsigned*>(b);
-        }
-        unsigned char* dst = dev ? out->published : b + ids_b + 256;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, 4, c->stream));
-        const long long per = (1ll << 31) / BLOCK;
-        const long long blocks = (count + BLOCK - 1) / BLOCK;
-        for (long long b0 = 0; b0 < blocks; b0 += per)
-            hipLaunchKernelGGL(k_vcls_gather, dim3((unsigned)std::min(per, blocks - b0)), dim3(BLOCK), 0, c->stream, src, d_ids, count,
-                               b0 * BLOCK, (unsigned)v.M, dst, d_bad);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-        src = dst;
-    }
-    if (!ids || !dev) {  // one copy of exactly count flags (zeros before the first classify)
-        if (src) HIP_TRY(hipMemcpyAsync(out->published, src, m, kind, c->stream));
-        else if (dev) HIP_TRY(hipMemsetAsync(out->published, 0, m, c->stream));
-        else std::memset(out->published, 0, m);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (h_bad && *h_bad) return fail(SDM_EINVAL, "id beyond the map's entries (the destinations are unspecified)");
-    return SDM_OK;
-}
-
-// ---- importing records and observations into the persistent voxel map (sdm_vmap_import.h) --------------------------------
-int sdm_vmap_import(sdm_ctx* c, const sdm_point_buffers* src, const sdm_vmap_fields* extra, long long count,
-                    sdm_vmap_import_delta* delta)
-{
-    if (delta) delta->total = delta->dropped = delta->first_created = delta->created = delta->updated = 0;
-    if (!c || !src) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (count < 0 || src->capacity < 0) return fail(SDM_EINVAL, "negative count or capacity");
-    if (count > src->capacity) return fail(SDM_EINVAL, "count exceeds capacity");
-    if (count > 0 && (!src->xyz || !src->rho_sigma)) return fail(SDM_EINVAL, "null source (xyz and rho_sigma are required)");
-    const int* s_tag = extra ? extra->tag : nullptr;
-    const unsigned* s_mult = extra ? extra->multiplicity : nullptr;
-    const bool dev = src->on_device != 0;
-    if (dev && (((uintptr_t)src->xyz | (uintptr_t)src->pixel | (uintptr_t)s_tag | (uintptr_t)s_mult) % 4 || (uintptr_t)src->rho_sigma % 8))
-        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel, tag, multiplicity: 4 B; rho_sigma: 8 B)");
-    unsigned* ids_dst = delta ? delta->dst_ids : nullptr;
-    unsigned* upd_dst = delta ? delta->updated_ids : nullptr;
-    if (upd_dst && delta->updated_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
-    if (delta && delta->on_device && ((uintptr_t)ids_dst | (uintptr_t)upd_dst) % 4)
-        return fail(SDM_EINVAL, "device buffer not aligned (dst_ids, updated_ids: 4 B)");
-    const long long R = count;
-    if (delta) delta->total = R, delta->first_created = v.M;
-    if (v.M + R > (1ll << 30)) return fail(SDM_EINVAL, "more than 2^30 entries and records: the voxel map's table would exceed 2^31 slots");
-    if (upd_dst && delta->updated_capacity < std::min(v.M, R))
-        return fail(SDM_EINVAL, "updated_capacity " + std::to_string(delta->updated_capacity) + " < min(entries, records) = " +
-                                    std::to_string(std::min(v.M, R)) + " (total and first_created filled)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (R == 0) {
-        v.calls++;
-        return SDM_OK;
-    }
-
-    // scratch, the staging of host sources and destinations, and growth: everything is allocated before anything is inserted
-    const size_t m = (size_t)R;
-    const long long vt = (R + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t where_b = ext_align(4 * m), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
-    const size_t blk_b = ext_align(8 * (size_t)vb);
-    size_t at = 512 + where_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b;
-    size_t xyz_off = 0, rs_off = 0, pix_off = 0, im_off = 0, tag_off = 0, mult_off = 0;
-    if (!dev) {
-        xyz_off = at, at += ext_align(12 * m);
-        rs_off = at, at += ext_align(8 * m);
-        if (src->pixel) pix_off = at, at += ext_align(4 * m);
-        if (src->intensity) im_off = at, at += ext_align(m);
-        if (s_tag) tag_off = at, at += ext_align(4 * m);
-        if (s_mult) mult_off = at, at += ext_align(4 * m);
-    }
-    int rc;
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, at))) return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256))) return rc;
-    const bool stage_out = delta && !delta->on_device;
-    const size_t ids_b = stage_out && ids_dst ? ext_align(4 * m) : 0;
-    if (stage_out && (ids_dst || upd_dst) && (rc = ext_grow_dev(&v.d_out, &v.out_bytes, ids_b + 4 * (size_t)std::min(v.M, R) + 4))) return rc;
-    if ((rc = vmap_grow(c, v.M + R))) return rc;
-    unsigned char* p = v.d_scratch;
-    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                           // {dropped, overflow}
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, updated, dropped, overflow, sum of m_r}
-    p += 512;
-    unsigned* d_where = reinterpret_cast<unsigned*>(p);
-    p += where_b;
-    unsigned* d_cnt_new = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_cnt_upd = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off_new = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned* d_off_upd = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum_new = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_new = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_bsum_upd = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_upd = reinterpret_cast<unsigned long long*>(p);
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
-
-    VimpSrc in{};
-    if (dev) {
-        in.xyz = src->xyz, in.rho_sigma = reinterpret_cast<const float2*>(src->rho_sigma), in.pixel = src->pixel;
-        in.intensity = src->intensity, in.tag = s_tag, in.multiplicity = s_mult;
-    } else {
-        unsigned char* b = v.d_scratch;
-        HIP_TRY(hipMemcpyAsync(b + xyz_off, src->xyz, 12 * m, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(b + rs_off, src->rho_sigma, 8 * m, hipMemcpyHostToDevice, c->stream));
-        if (src->pixel) HIP_TRY(hipMemcpyAsync(b + pix_off, src->pixel, 4 * m, hipMemcpyHostToDevice, c->stream));
-        if (src->intensity) HIP_TRY(hipMemcpyAsync(b + im_off, src->intensity, m, hipMemcpyHostToDevice, c->stream));
-        if (s_tag) HIP_TRY(hipMemcpyAsync(b + tag_off, s_tag, 4 * m, hipMemcpyHostToDevice, c->stream));
-        if (s_mult) HIP_TRY(hipMemcpyAsync(b + mult_off, s_mult, 4 * m, hipMemcpyHostToDevice, c->stream));
-        in.xyz = reinterpret_cast<const float*>(b + xyz_off);
-        in.rho_sigma = reinterpret_cast<const float2*>(b + rs_off);
-        in.pixel = src->pixel ? reinterpret_cast<const unsigned*>(b + pix_off) : nullptr;
-        in.intensity = src->intensity ? b + im_off : nullptr;
-        in.tag = s_tag ? reinterpret_cast<const int*>(b + tag_off) : nullptr;
-        in.multiplicity = s_mult ? reinterpret_cast<const unsigned*>(b + mult_off) : nullptr;
-    }
-
-    HIP_TRY(hipMemsetAsync(d_ctr, 0, 8, c->stream));
-    HIP_TRY(hipMemsetAsync(d_tot + 4, 0, 8, c->stream));
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long pblocks = (R + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vimp_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, in, R, b0 * BLOCK,
-                           v.inv, v.tb, d_where, d_ctr, d_tot + 4);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where, R,
-                           t0, d_cnt_new, d_cnt_upd);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_new, vt, d_off_new, d_bsum_new);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_new, (int)vb, d_boff_new);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_upd, vt, d_off_upd, d_bsum_upd);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_upd, (int)vb, d_boff_upd);
-    hipLaunchKernelGGL(k_vmap_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_new, d_boff_new, d_off_upd, d_boff_upd, d_ctr,
-                       d_tot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: created and updated
-    if (h_tot[3]) return fail(SDM_EHIP, "voxel map table overflow");
-    const long long created = (long long)h_tot[0], updated = (long long)h_tot[1], dropped = (long long)h_tot[2];
-    const long long stored = (long long)h_tot[4];
-
-    unsigned* d_ids = !ids_dst ? nullptr : stage_out ? reinterpret_cast<unsigned*>(v.d_out) : ids_dst;
-    unsigned* d_upd = !upd_dst ? nullptr : stage_out ? reinterpret_cast<unsigned*>(v.d_out + ids_b) : upd_dst;
-    const unsigned first_created = (unsigned)v.M, epoch = (unsigned)(v.calls + 1);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_ids, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
-                           first_created, R, t0, d_off_new, d_boff_new);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vimp_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
-                           first_created, R, t0, d_off_upd, d_boff_upd, d_upd);
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vimp_write, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.tb, v.rec, d_where,
-                           first_created, epoch, R, b0 * BLOCK, in, d_ids, (const unsigned*)nullptr);
-    HIP_TRY(hipGetLastError());
-    if (stage_out && ids_dst) HIP_TRY(hipMemcpyAsync(ids_dst, d_ids, 4 * m, hipMemcpyDeviceToHost, c->stream));
-    if (stage_out && upd_dst && updated)
-        HIP_TRY(hipMemcpyAsync(upd_dst, d_upd, 4 * (size_t)updated, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    v.M += created;
-    v.points += stored;
-    v.dropped += dropped;
-    v.calls++;
-    if (delta) delta->created = created, delta->updated = updated, delta->dropped = dropped;
-    return SDM_OK;
-}
-
-int sdm_vmap_import_observations(sdm_ctx* c, long long count, sdm_vmap_obs_import* io)
-{
-    if (io) io->total = io->rejected = io->first_created = io->created = 0;
-    if (!c || !io) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    sdm_ctx::Vmap::Obs& o = v.obs;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (count < 0) return fail(SDM_EINVAL, "negative count");
-    if (io->map_count < 0) return fail(SDM_EINVAL, "negative map_count");
-    if (count > 0 && (!io->entry || !io->tag)) return fail(SDM_EINVAL, "null source (entry and tag are required)");
-    const bool dev = io->on_device != 0;
-    if (dev && ((uintptr_t)io->entry | (uintptr_t)io->tag | (uintptr_t)io->entry_map) % 4)
-        return fail(SDM_EINVAL, "device buffer not aligned (entry, tag, entry_map: 4 B)");
-    const long long P = count;
-    io->total = P;
-    io->first_created = o.E;
-    if (o.E + P > (1ll << 30))
-        return fail(SDM_EINVAL, "more than 2^30 observations and pairs: the observation set would exceed 2^31 slots");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (P == 0) {
-        o.calls++;
-        return SDM_OK;
-    }
-
-    // scratch, the staging of host sources, pinned mirror and growth: everything is allocated before anything is inserted
-    const size_t m = (size_t)P, mm = io->entry_map ? (size_t)io->map_count : 0;
-    const long long vt = (P + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t where_b = ext_align(4 * m), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1)),
-                 blk_b = ext_align(8 * (size_t)vb);
-    size_t at = 512 + where_b + tcnt_b + toff_b + 2 * blk_b;
-    const size_t ent_off = at, tag_off = ent_off + ext_align(4 * m), map_off = tag_off + ext_align(4 * m);
-    if (!dev) at = map_off + ext_align(4 * mm);
-    int rc;
-    if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, at))) return rc;
-    if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
-    // the tags a list may now hold bound its length (sdm_vmap_fetch_cameras' scan): device tags are read back for that, into
-    // a buffer made here, before anything is inserted
-    std::vector<int> back;
-    if (dev) {
-        try {
-            back.resize(m);
-        } catch (const std::bad_alloc&) {
-            return fail(SDM_EHIP, "host allocation of " + std::to_string(4 * m) + " B for the tags failed");
-        }
-    }
-    if ((rc = vobs_grow(c, o.E + P))) return rc;
-    unsigned char* p = o.d_scratch;
-    unsigned long long* d_ctr = reinterpret_cast<unsigned long long*>(p + 64);   // {rejected, stored or found, overflow}
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, rejected, stored or found, overflow}
-    p += 512;
-    unsigned* d_where = reinterpret_cast<unsigned*>(p);
-    p += where_b;
-    unsigned* d_cnt = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
-    const unsigned* d_entry = io->entry;
-    const int* d_tag = io->tag;
-    const unsigned* d_map = io->entry_map;
-    if (!dev) {
-        unsigned char* b = o.d_scratch;
-        HIP_TRY(hipMemcpyAsync(b + ent_off, io->entry, 4 * m, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(b + tag_off, io->tag, 4 * m, hipMemcpyHostToDevice, c->stream));
-        if (mm) HIP_TRY(hipMemcpyAsync(b + map_off, io->entry_map, 4 * mm, hipMemcpyHostToDevice, c->stream));
-        d_entry = reinterpret_cast<const unsigned*>(b + ent_off);
-        d_tag = reinterpret_cast<const int*>(b + tag_off);
-        if (d_map) d_map = reinterpret_cast<const unsigned*>(b + map_off);  // (map_count == 0: never read)
-    }
-    HIP_TRY(hipMemsetAsync(d_ctr, 0, 24, c->stream));
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long pblocks = (P + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, d_entry,
-                           d_tag, d_map, io->map_count, P, b0 * BLOCK, (unsigned)v.M, o.tb, d_where, d_ctr,
-                           (const unsigned char*)nullptr);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_where, P, t0,
-                           d_cnt);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt, vt, d_off, d_bsum);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum, (int)vb, d_boff);
-    hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off, d_boff, d_ctr, d_tot);
-    HIP_TRY(hipGetLastError());
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(o.h_pin);
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 32, hipMemcpyDeviceToHost, c->stream));
-    const int* h_tag = io->tag;
-    if (dev) {
-        HIP_TRY(hipMemcpyAsync(back.data(), d_tag, 4 * m, hipMemcpyDeviceToHost, c->stream));
-        h_tag = back.data();
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: created
-    if (h_tot[3]) return fail(SDM_EHIP, "observation set overflow");
-    const long long created = (long long)h_tot[0];
-
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log, o.last_obs,
-                           o.ncam, d_where, (unsigned)o.E, P, t0, d_off, d_boff);
-    HIP_TRY(hipGetLastError());
-    // every tag >= 0 of the call counts, a rejected pair's too (its entry is not resolved here): `seen` is an upper bound of
-    // the tags the lists hold, which is all sdm_vmap_fetch_cameras' refusal needs, and the header says so
-    int last = -1;
-    for (size_t k = 0; k < m; k++) {  // (on the host, beside the commit; one binary search per change of tag)
-        const int t = h_tag[k];
-        if (t < 0 || t == last) continue;
-        last = t;
-        const auto it = std::lower_bound(o.seen.begin(), o.seen.end(), t);
-        if (it == o.seen.end() || *it != t) o.seen.insert(it, t);
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    io->rejected = (long long)h_tot[1];
-    io->created = created;
-    o.E += created;
-    o.calls++;
-    return SDM_OK;
-}
-
-// ---- re-placing the persistent voxel map under new poses (sdm_vmap_repose.h) ----------------------------------------------
-namespace {
-// device blocks made for a repose; whatever is still held when the call leaves is freed (after the swap: the old ones)
-struct VrepBlocks {
-    unsigned char *rec = nullptr, *evid = nullptr, *pub = nullptr;
-    ~VrepBlocks()
-    {
-        (void)hipFree(rec);
-        (void)hipFree(evid);
-        (void)hipFree(pub);
-    }
-};
-}  // namespace
-
-int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, const float* Tcw, sdm_vmap_repose_delta* delta)
-{
-    if (delta)
-        delta->examined = delta->reposed = delta->moved = delta->dropped = delta->merged = delta->voxels =
-            delta->observations_before = delta->observations = 0;
-    if (!c || !delta) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    sdm_ctx::Vmap::Obs& o = v.obs;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (n_poses < 0) return fail(SDM_EINVAL, "negative n_poses");
-    if (n_poses > 0 && (!tags || !K || !Tcw)) return fail(SDM_EINVAL, "null pose table (tags, K and Tcw are required)");
-    if (delta->carry != 0 && delta->carry != 1) return fail(SDM_EINVAL, "carry must be 0 or 1");
-    const size_t np = (size_t)n_poses;
-    std::vector<int> order;  // the table's rows by ascending tag
-    try {
-        order.resize(np);
-    } catch (const std::bad_alloc&) {
-        return fail(SDM_EHIP, "host allocation for the pose table failed");
-    }
-    for (size_t p = 0; p < np; p++) {
-        if (tags[p] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
-        order[p] = (int)p;
-    }
-    std::sort(order.begin(), order.end(), [tags](int a, int b) { return tags[a] < tags[b]; });
-    for (size_t p = 1; p < np; p++)
-        if (tags[order[p]] == tags[order[p - 1]]) return fail(SDM_EINVAL, "tag " + std::to_string(tags[order[p]]) + " listed twice");
-    unsigned* remap_dst = delta->remap;
-    const bool remap_dev = remap_dst && delta->on_device;
-    if (remap_dev && (uintptr_t)remap_dst % 4) return fail(SDM_EINVAL, "device buffer not aligned (remap: 4 B)");
-    const long long M = v.M, E = o.E;
-    delta->examined = M;
-    if (remap_dst && delta->remap_capacity < M)
-        return fail(SDM_EINVAL, "remap_capacity " + std::to_string(delta->remap_capacity) + " < entries = " + std::to_string(M) +
-                                    " (examined filled)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    delta->observations_before = delta->observations = E;
-    if (M == 0) {  // (no entry: no pair, no counter, no flag)
-        v.calls++;
-        return SDM_OK;
-    }
-
-    // scratch, pose table, the second set of records (with carry: of counters and flags), the log's scratch: everything is
-    // allocated before anything is written
-    const bool carry = delta->carry == 1;
-    const size_t m = (size_t)M;
-    const long long vt = (M + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t where_b = ext_align(4 * m), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
-    const size_t blk_b = ext_align(8 * (size_t)vb);
-    size_t at = 512 + where_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b;
-    const size_t xyz_off = at;
-    at += ext_align(12 * m);
-    const size_t tags_b = ext_align(4 * np), poses_b = ext_align(sizeof(KfMeta) * np);
-    const size_t tab_off = at;
-    at += tags_b + poses_b;
-    const size_t remap_off = at;
-    if (!remap_dev) at += ext_align(4 * m);
-    int rc;
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, at))) return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tags_b + poses_b))) return rc;
-    const long long ot = (E + EXT_TILE - 1) / EXT_TILE;
-    const long long ob = (ot + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t owhere_b = ext_align(4 * (size_t)E), otcnt_b = ext_align(4 * (size_t)ot), otoff_b = ext_align(4 * (size_t)(ot + 1)),
-                 oblk_b = ext_align(8 * (size_t)ob);
-    if (E > 0) {
-        if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, 512 + owhere_b + otcnt_b + otoff_b + 2 * oblk_b))) return rc;
-        if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
-    }
-    VrepBlocks nb;
-    VmapRecords nr{};
-    if ((rc = vmap_make_records(v.rec_cap, &nb.rec, &nr))) return rc;
-    unsigned long long *ncr = nullptr, *nen = nullptr;
-    if (carry && v.d_evid && (rc = vmap_make_evidence(c, v.rec_cap, &nb.evid, &ncr, &nen))) return rc;
-    if (carry && v.cls.d_pub && (rc = vmap_make_published(c, v.rec_cap, &nb.pub))) return rc;
-
-    unsigned char* p = v.d_scratch;
-    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                            // {dropped, overflow}
-    unsigned long long* d_rep = reinterpret_cast<unsigned long long*>(p + 64);   // {reposed, moved, published}
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // {created, updated, dropped, overflow, sum of m_i}
-    p += 512;
-    unsigned* d_where = reinterpret_cast<unsigned*>(p);
-    p += where_b;
-    unsigned* d_cnt_new = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_cnt_upd = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off_new = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned* d_off_upd = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum_new = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_new = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_bsum_upd = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_upd = reinterpret_cast<unsigned long long*>(p);
-    float* d_xyz = reinterpret_cast<float*>(v.d_scratch + xyz_off);
-    int* d_tags = reinterpret_cast<int*>(v.d_scratch + tab_off);
-    KfMeta* d_poses = reinterpret_cast<KfMeta*>(v.d_scratch + tab_off + tags_b);
-    unsigned* d_remap = remap_dev ? remap_dst : reinterpret_cast<unsigned*>(v.d_scratch + remap_off);
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);  // [0..5) the import's totals, [8..11) d_rep
-    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
-    KfMeta* h_poses = reinterpret_cast<KfMeta*>(v.h_pin + 256 + tags_b);
-    for (size_t q = 0; q < np; q++) {
-        const size_t s = (size_t)order[q];
-        h_tags[q] = tags[s];
-        std::memset(&h_poses[q], 0, sizeof(KfMeta));
-        fill_meta(h_poses[q], K + 4 * s, Tcw + 12 * s);
-    }
-
-    // the new xyz of every old entry
-    HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 512, c->stream));
-    if (np) HIP_TRY(hipMemcpyAsync(d_tags, h_tags, tags_b + poses_b, hipMemcpyHostToDevice, c->stream));
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long pblocks = (M + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vrep_project, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.rec, M,
-                           b0 * BLOCK, d_tags, d_poses, n_poses, d_xyz, d_rep);
-    // one import of the old records, at their new xyz, into the emptied table and the second set of records
-    HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
-    HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
-    VimpSrc in{};
-    in.xyz = d_xyz, in.rho_sigma = v.rec.rho_sigma, in.pixel = v.rec.pixel;
-    in.intensity = v.rec.intensity, in.tag = v.rec.tag, in.multiplicity = v.rec.multiplicity;
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vimp_insert, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, in, M, b0 * BLOCK,
-                           v.inv, v.tb, d_where, d_ctr, d_tot + 4);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where, M, t0,
-                           d_cnt_new, d_cnt_upd);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_new, vt, d_off_new, d_bsum_new);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_new, (int)vb, d_boff_new);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_upd, vt, d_off_upd, d_bsum_upd);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_upd, (int)vb, d_boff_upd);
-    hipLaunchKernelGGL(k_vmap_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_new, d_boff_new, d_off_upd, d_boff_upd, d_ctr,
-                       d_tot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: the new M
-    if (h_tot[3]) return fail(SDM_EHIP, "voxel map table overflow");
-    const long long M2 = (long long)h_tot[0], dropped = (long long)h_tot[2];
-
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vmap_ids, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where, 0u, M,
-                           t0, d_off_new, d_boff_new);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vimp_commit, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where, 0u,
-                           M, t0, d_off_upd, d_boff_upd, (unsigned*)nullptr);
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vimp_write, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.tb, nr, d_where,
-                           0u, 0u, M, b0 * BLOCK, in, d_remap, (const unsigned*)v.rec.epoch);
-    // counters and flags: carried through remap into the second set, or back to 0 where they are
-    const size_t evid_b = 2 * ext_align(8 * (size_t)v.rec_cap);
-    if (carry && (nb.evid || nb.pub)) {
-        for (long long b0 = 0; b0 < pblocks; b0 += per)
-            hipLaunchKernelGGL(k_vrep_carry, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, d_remap, M,
-                               b0 * BLOCK, nb.evid ? v.crossings : nullptr, nb.evid ? v.ends : nullptr, ncr, nen,
-                               nb.pub ? v.cls.d_pub : nullptr, nb.pub);
-        if (nb.pub) {
-            const long long cblocks = (M2 + BLOCK - 1) / BLOCK;
-            for (long long b0 = 0; b0 < cblocks; b0 += per)
-                hipLaunchKernelGGL(k_vrep_count, dim3((unsigned)std::min(per, cblocks - b0)), dim3(BLOCK), 0, c->stream, nb.pub, M2,
-                                   b0 * BLOCK, d_rep + 2);
-        }
-    } else if (!carry) {
-        if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, evid_b, c->stream));
-        if (v.cls.d_pub) HIP_TRY(hipMemsetAsync(v.cls.d_pub, 0, (size_t)v.rec_cap, c->stream));
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_tot + 8, d_rep, 24, hipMemcpyDeviceToHost, c->stream));
-    if (remap_dst && !remap_dev) HIP_TRY(hipMemcpyAsync(remap_dst, d_remap, 4 * m, hipMemcpyDeviceToHost, c->stream));
-
-    // the log: the old pairs, in log order, through remap into the emptied set, in place
-    unsigned long long* h_otot = nullptr;
-    if (E > 0) {
-        unsigned char* q = o.d_scratch;
-        unsigned long long* d_octr = reinterpret_cast<unsigned long long*>(q + 64);   // {rejected, stored or found, overflow}
-        unsigned long long* d_otot = reinterpret_cast<unsigned long long*>(q + 256);  // {created, rejected, stored or found, overflow}
-        q += 512;
-        unsigned* d_owhere = reinterpret_cast<unsigned*>(q);
-        q += owhere_b;
-        unsigned* d_ocnt = reinterpret_cast<unsigned*>(q);
-        q += otcnt_b;
-        unsigned* d_ooff = reinterpret_cast<unsigned*>(q);
-        q += otoff_b;
-        unsigned long long* d_obsum = reinterpret_cast<unsigned long long*>(q);
-        q += oblk_b;
-        unsigned long long* d_oboff = reinterpret_cast<unsigned long long*>(q);
-        const size_t b4 = ext_align(4 * (size_t)v.rec_cap);
-        HIP_TRY(hipMemsetAsync(o.d_table, 0xff, 20 * (size_t)o.cap, c->stream));
-        HIP_TRY(hipMemsetAsync(o.d_ent, 0xff, b4, c->stream));
-        HIP_TRY(hipMemsetAsync(o.d_ent + b4, 0, b4, c->stream));
-        HIP_TRY(hipMemsetAsync(d_octr, 0, 24, c->stream));
-        const long long eblocks = (E + BLOCK - 1) / BLOCK;
-        for (long long b0 = 0; b0 < eblocks; b0 += per)
-            hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
-                               (const unsigned*)o.log.entry, (const int*)o.log.tag, (const unsigned*)d_remap, M, E, b0 * BLOCK,
-                               (unsigned)M2, o.tb, d_owhere, d_octr, (const unsigned char*)nullptr);
-        for (long long t0 = 0; t0 < ot; t0 += per)
-            hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_owhere, E, t0,
-                               d_ocnt);
-        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_ocnt, ot, d_ooff, d_obsum);
-        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_obsum, (int)ob, d_oboff);
-        hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, ot, d_ooff, d_oboff, d_octr, d_otot);
-        for (long long t0 = 0; t0 < ot; t0 += per)
-            hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log,
-                               o.last_obs, o.ncam, d_owhere, 0u, E, t0, d_ooff, d_oboff);
-        HIP_TRY(hipGetLastError());
-        h_otot = reinterpret_cast<unsigned long long*>(o.h_pin);
-        HIP_TRY(hipMemcpyAsync(h_otot, d_otot, 32, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end
-    if (h_otot && h_otot[3]) return fail(SDM_EHIP, "observation set overflow");
-
-    // the second sets become the map's; the old ones go with `nb`
-    std::swap(v.d_rec, nb.rec);
-    v.rec = nr;
-    if (nb.evid) {
-        std::swap(v.d_evid, nb.evid);
-        v.crossings = ncr;
-        v.ends = nen;
-    }
-    if (nb.pub) std::swap(v.cls.d_pub, nb.pub);
-    v.cls.published = carry ? (long long)h_tot[10] : 0;
-    v.M = M2;
-    v.calls++;
-    if (h_otot) o.E = (long long)h_otot[0];
-    delta->reposed = (long long)h_tot[8];
-    delta->moved = (long long)h_tot[9];
-    delta->dropped = dropped;
-    delta->voxels = M2;
-    delta->merged = M - dropped - M2;
-    delta->observations = o.E;
-    return SDM_OK;
-}
-
-// ---- retiring keyframes from the persistent voxel map (sdm_vmap_retire.h) -------------------------------------------------
-int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vmap_retire_delta* delta)
-{
-    if (delta)
-        delta->examined = delta->dropped = delta->dropped_were_published = delta->orphaned = delta->voxels =
-            delta->observations_before = delta->observations = delta->removed = delta->published_total = 0;
-    if (!c || !delta) return fail(SDM_EINVAL, "null argument");
-    sdm_ctx::Vmap& v = c->vmap;
-    sdm_ctx::Vmap::Obs& o = v.obs;
-    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
-    if (n_tags < 0) return fail(SDM_EINVAL, "negative n_tags");
-    if (n_tags > 0 && !tags) return fail(SDM_EINVAL, "null tags");
-    if (delta->mode != SDM_VMAP_RETIRE_WINNER && delta->mode != SDM_VMAP_RETIRE_UNOBSERVED)
-        return fail(SDM_EINVAL, "mode must be SDM_VMAP_RETIRE_WINNER or SDM_VMAP_RETIRE_UNOBSERVED");
-    if (delta->carry != 0 && delta->carry != 1) return fail(SDM_EINVAL, "carry must be 0 or 1");
-    if (commit != 0 && commit != 1) return fail(SDM_EINVAL, "commit must be 0 or 1");
-    const size_t nt = (size_t)n_tags;
-    std::vector<int> sorted;  // R, ascending
-    try {
-        sorted.assign(tags, tags + nt);
-    } catch (const std::bad_alloc&) {
-        return fail(SDM_EHIP, "host allocation for the tags failed");
-    }
-    for (size_t p = 0; p < nt; p++)
-        if (sorted[p] < 0) return fail(SDM_EINVAL, "tag outside [0, 2^31)");
-    std::sort(sorted.begin(), sorted.end());
-    for (size_t p = 1; p < nt; p++)
-        if (sorted[p] == sorted[p - 1]) return fail(SDM_EINVAL, "tag " + std::to_string(sorted[p]) + " listed twice");
-    unsigned *remap_dst = delta->remap, *drop_dst = delta->dropped_ids, *rem_dst = delta->removed_entry;
-    unsigned char* dpub_dst = delta->dropped_published;
-    int* rtag_dst = delta->removed_tag;
-    if ((remap_dst && delta->remap_capacity < 0) || ((drop_dst || dpub_dst) && delta->dropped_capacity < 0) ||
-        ((rem_dst || rtag_dst) && delta->removed_capacity < 0))
-        return fail(SDM_EINVAL, "negative capacity");
-    if (dpub_dst && !drop_dst) return fail(SDM_EINVAL, "dropped_published without dropped_ids");
-    if (rtag_dst && !rem_dst) return fail(SDM_EINVAL, "removed_tag without removed_entry");
-    const bool dev = delta->on_device != 0;
-    if (dev && ((uintptr_t)remap_dst | (uintptr_t)drop_dst | (uintptr_t)rem_dst | (uintptr_t)rtag_dst) % 4)
-        return fail(SDM_EINVAL, "device buffer not aligned (remap, dropped_ids, removed_entry, removed_tag: 4 B)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const long long M = v.M, E = o.E;
-    const bool unobserved = delta->mode == SDM_VMAP_RETIRE_UNOBSERVED, carry = delta->carry == 1;
-    delta->examined = M;
-    delta->observations_before = E;
-    if (M == 0) {  // (no entry: no pair, no counter, no flag)
-        if (commit) v.calls++;
-        return SDM_OK;
-    }
-
-    // the marking phase's scratch and the log's, R on both sides of the link, the second sets: everything but the staging
-    // of host lists, which follows the counts, is allocated before anything is written
-    const size_t m = (size_t)M, e = (size_t)E;
-    const long long vt = (M + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t tags_b = ext_align(4 * std::max(nt, (size_t)1)), mark_b = ext_align(m), tcnt_b = ext_align(4 * (size_t)vt),
-                 toff_b = ext_align(4 * (size_t)(vt + 1)), blk_b = ext_align(8 * (size_t)vb);
-    const bool remap_own = !(dev && remap_dst);
-    int rc;
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes,
-                           512 + tags_b + 2 * mark_b + 2 * tcnt_b + 2 * toff_b + 4 * blk_b + (remap_own ? ext_align(4 * m) : 0))))
-        return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tags_b))) return rc;
-    const long long ot = (E + EXT_TILE - 1) / EXT_TILE;
-    const long long ob = (ot + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t owhere_b = ext_align(4 * e), omark_b = ext_align(e), otcnt_b = ext_align(4 * (size_t)ot),
-                 otoff_b = ext_align(4 * (size_t)(ot + 1)), oblk_b = ext_align(8 * (size_t)ob);
-    if (E > 0) {
-        if ((rc = ext_grow_dev(&o.d_scratch, &o.scratch_bytes, 512 + owhere_b + omark_b + 2 * otcnt_b + 2 * otoff_b + 4 * oblk_b)))
-            return rc;
-        if ((rc = ext_grow_host(&o.h_pin, &o.pin_bytes, 256))) return rc;
-    }
-    VrepBlocks nb;
-    VmapRecords nr{};
-    unsigned long long *ncr = nullptr, *nen = nullptr;
-    if (commit) {
-        if ((rc = vmap_make_records(v.rec_cap, &nb.rec, &nr))) return rc;
-        if (carry && v.d_evid && (rc = vmap_make_evidence(c, v.rec_cap, &nb.evid, &ncr, &nen))) return rc;
-        if (carry && v.cls.d_pub && (rc = vmap_make_published(c, v.rec_cap, &nb.pub))) return rc;
-    }
-
-    unsigned char* p = v.d_scratch;
-    unsigned* d_ctr = reinterpret_cast<unsigned*>(p);                            // {-, overflow}
-    unsigned long long* d_cnt3 = reinterpret_cast<unsigned long long*>(p + 64);  // k_vret_entries' three counters
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p + 256);  // k_vret_totals' seven
-    p += 512;
-    int* d_tags = reinterpret_cast<int*>(p);
-    p += tags_b;
-    unsigned char* d_seen = p;
-    p += mark_b;
-    unsigned char* d_emark = p;
-    p += mark_b;
-    unsigned* d_cnt_s = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_cnt_d = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_off_s = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned* d_off_d = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum_s = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_s = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_bsum_d = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff_d = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned* d_remap = remap_own ? reinterpret_cast<unsigned*>(p) : remap_dst;
-    // the log's scratch: the import's part first (as sdm_vmap_repose lays it out), then the marks and their two scans
-    unsigned long long *d_octr = nullptr, *d_otot = nullptr, *d_obsum = nullptr, *d_oboff = nullptr;
-    unsigned long long *d_bsum_r = nullptr, *d_boff_r = nullptr, *d_bsum_v = nullptr, *d_boff_v = nullptr;
-    unsigned *d_owhere = nullptr, *d_ocnt = nullptr, *d_ooff = nullptr, *d_cnt_r = nullptr, *d_cnt_v = nullptr, *d_off_r = nullptr,
-             *d_off_v = nullptr;
-    unsigned char* d_pmark = nullptr;
-    if (E > 0) {
-        unsigned char* q = o.d_scratch;
-        d_octr = reinterpret_cast<unsigned long long*>(q + 64);   // {rejected, stored or found, overflow}
-        d_otot = reinterpret_cast<unsigned long long*>(q + 256);  // {created, rejected, stored or found, overflow}
-        q += 512;
-        d_owhere = reinterpret_cast<unsigned*>(q);
-        q += owhere_b;
-        d_ocnt = reinterpret_cast<unsigned*>(q);
-        q += otcnt_b;
-        d_ooff = reinterpret_cast<unsigned*>(q);
-        q += otoff_b;
-        d_obsum = reinterpret_cast<unsigned long long*>(q);
-        q += oblk_b;
-        d_oboff = reinterpret_cast<unsigned long long*>(q);
-        q += oblk_b;
-        d_pmark = q;
-        q += omark_b;
-        d_cnt_r = d_ocnt, d_off_r = d_ooff, d_bsum_r = d_obsum, d_boff_r = d_oboff;  // (the import's are free until the log is rebuilt)
-        d_cnt_v = reinterpret_cast<unsigned*>(q);
-        q += otcnt_b;
-        d_off_v = reinterpret_cast<unsigned*>(q);
-        q += otoff_b;
-        d_bsum_v = reinterpret_cast<unsigned long long*>(q);
-        q += oblk_b;
-        d_boff_v = reinterpret_cast<unsigned long long*>(q);
-    }
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
-    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
-    if (nt) std::memcpy(h_tags, sorted.data(), 4 * nt);
-
-    // the marking phase: reads the map, writes scratch
-    HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 512, c->stream));
-    if (nt) HIP_TRY(hipMemcpyAsync(d_tags, h_tags, 4 * nt, hipMemcpyHostToDevice, c->stream));
-    if (unobserved) HIP_TRY(hipMemsetAsync(d_seen, 0, m, c->stream));
-    const long long per = (1ll << 31) / BLOCK;  // workgroups of one dispatch (for_ref_slices)
-    const long long pblocks = (M + BLOCK - 1) / BLOCK, eblocks = (E + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < eblocks; b0 += per)
-        hipLaunchKernelGGL(k_vret_pairs, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
-                           (const unsigned*)o.log.entry, (const int*)o.log.tag, E, b0 * BLOCK, (unsigned)M, (const int*)d_tags, n_tags,
-                           d_pmark, unobserved ? d_seen : (unsigned char*)nullptr);
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vret_entries, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream,
-                           (const int*)v.rec.tag, (const unsigned char*)v.cls.d_pub,
-                           unobserved ? (const unsigned char*)d_seen : (const unsigned char*)nullptr, M, b0 * BLOCK,
-                           (const int*)d_tags, n_tags, d_emark, d_cnt3);
-    for (long long t0 = 0; t0 < vt; t0 += per)
-        hipLaunchKernelGGL(k_vret_count, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream,
-                           (const unsigned char*)d_emark, 1u, 1u, 0u, M, t0, d_cnt_s, d_cnt_d);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_s, vt, d_off_s, d_bsum_s);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_s, (int)vb, d_boff_s);
-    hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)vb), dim3(BLOCK), 0, c->stream, d_cnt_d, vt, d_off_d, d_bsum_d);
-    hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_d, (int)vb, d_boff_d);
-    if (E > 0) {
-        for (long long b0 = 0; b0 < eblocks; b0 += per)
-            hipLaunchKernelGGL(k_vret_vanish, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
-                               (const unsigned*)o.log.entry, E, b0 * BLOCK, (unsigned)M, (const unsigned char*)d_emark, d_pmark);
-        for (long long t0 = 0; t0 < ot; t0 += per)
-            hipLaunchKernelGGL(k_vret_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream,
-                               (const unsigned char*)d_pmark, 3u, (unsigned)VRET_REMOVED, (unsigned)VRET_VANISHED, E, t0, d_cnt_r,
-                               d_cnt_v);
-        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_cnt_r, ot, d_off_r, d_bsum_r);
-        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_r, (int)ob, d_boff_r);
-        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_cnt_v, ot, d_off_v, d_bsum_v);
-        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_bsum_v, (int)ob, d_boff_v);
-    }
-    hipLaunchKernelGGL(k_vret_totals, dim3(1), dim3(64), 0, c->stream, vt, d_off_s, d_boff_s, d_off_d, d_boff_d, E > 0 ? ot : 0ll,
-                       d_off_r, d_boff_r, d_off_v, d_boff_v, d_cnt3, d_tot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 56, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the first wait: the counts
-    const long long M2 = (long long)h_tot[0], dropped = (long long)h_tot[1], removed = (long long)h_tot[2],
-                    vanished = (long long)h_tot[3];
-    delta->dropped = dropped;
-    delta->removed = removed;
-    delta->orphaned = (long long)h_tot[4];
-    delta->dropped_were_published = (long long)h_tot[5];
-    delta->voxels = M2;
-    delta->observations = E - removed - vanished;
-    delta->published_total = carry ? (long long)h_tot[6] : 0;
-    if (remap_dst && delta->remap_capacity < M)
-        return fail(SDM_EINVAL, "remap_capacity " + std::to_string(delta->remap_capacity) + " < entries = " + std::to_string(M) +
-                                    " (the counts are filled)");
-    if (drop_dst && delta->dropped_capacity < dropped)
-        return fail(SDM_EINVAL, "dropped_capacity " + std::to_string(delta->dropped_capacity) + " < " + std::to_string(dropped) +
-                                    " dropped entries (the counts are filled)");
-    if (rem_dst && delta->removed_capacity < removed)
-        return fail(SDM_EINVAL, "removed_capacity " + std::to_string(delta->removed_capacity) + " < " + std::to_string(removed) +
-                                    " removed pairs (the counts are filled)");
-
-    // the lists (nothing of the map has changed yet: a failure here leaves the state as it was)
-    const bool list_drop = drop_dst && dropped, list_rem = rem_dst && removed;
-    unsigned *d_drop = list_drop ? drop_dst : nullptr, *d_rem = list_rem ? rem_dst : nullptr;
-    unsigned char* d_dpub = list_drop ? dpub_dst : nullptr;
-    int* d_rtag = list_rem ? rtag_dst : nullptr;
-    if (!dev && (list_drop || list_rem)) {
-        const size_t drop_b = list_drop ? ext_align(4 * (size_t)dropped) : 0, dpub_b = list_drop && dpub_dst ? ext_align((size_t)dropped) : 0,
-                     rem_b = list_rem ? ext_align(4 * (size_t)removed) : 0;
-        if ((rc = ext_grow_dev(&v.d_out, &v.out_bytes, drop_b + dpub_b + 2 * rem_b))) return rc;
-        if (list_drop) d_drop = reinterpret_cast<unsigned*>(v.d_out);
-        if (list_drop && dpub_dst) d_dpub = v.d_out + drop_b;
-        if (list_rem) d_rem = reinterpret_cast<unsigned*>(v.d_out + drop_b + dpub_b);
-        if (list_rem && rtag_dst) d_rtag = reinterpret_cast<int*>(v.d_out + drop_b + dpub_b + rem_b);
-    }
-    if (commit || remap_dst || list_drop)
-        for (long long t0 = 0; t0 < vt; t0 += per)
-            hipLaunchKernelGGL(k_vret_remap, dim3((unsigned)std::min(per, vt - t0)), dim3(BLOCK), 0, c->stream,
-                               (const unsigned char*)d_emark, M, t0, d_off_s, d_boff_s, d_off_d, d_boff_d,
-                               commit || remap_dst ? d_remap : (unsigned*)nullptr, d_drop, d_dpub);
-    if (list_rem)
-        for (long long t0 = 0; t0 < ot; t0 += per)
-            hipLaunchKernelGGL(k_vret_removed, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream,
-                               (const unsigned char*)d_pmark, (const unsigned*)o.log.entry, (const int*)o.log.tag, E, t0, d_off_r,
-                               d_boff_r, d_rem, d_rtag);
-    HIP_TRY(hipGetLastError());
-    if (!dev) {  // (the copies are queued behind the kernels that fill their sources and before anything overwrites them)
-        if (remap_dst) HIP_TRY(hipMemcpyAsync(remap_dst, d_remap, 4 * m, hipMemcpyDeviceToHost, c->stream));
-        if (list_drop) HIP_TRY(hipMemcpyAsync(drop_dst, d_drop, 4 * (size_t)dropped, hipMemcpyDeviceToHost, c->stream));
-        if (list_drop && dpub_dst) HIP_TRY(hipMemcpyAsync(dpub_dst, d_dpub, (size_t)dropped, hipMemcpyDeviceToHost, c->stream));
-        if (list_rem) HIP_TRY(hipMemcpyAsync(rem_dst, d_rem, 4 * (size_t)removed, hipMemcpyDeviceToHost, c->stream));
-        if (list_rem && rtag_dst) HIP_TRY(hipMemcpyAsync(rtag_dst, d_rtag, 4 * (size_t)removed, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (!commit) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SDM_OK;
-    }
-
-    // records (with carry: counters and flags) into the second set; the table emptied and filled from the new records
-    for (long long b0 = 0; b0 < pblocks; b0 += per)
-        hipLaunchKernelGGL(k_vret_records, dim3((unsigned)std::min(per, pblocks - b0)), dim3(BLOCK), 0, c->stream, v.rec, nr,
-                           (const unsigned*)d_remap, M, b0 * BLOCK, nb.evid ? (const unsigned long long*)v.crossings : nullptr,
-                           nb.evid ? (const unsigned long long*)v.ends : nullptr, ncr, nen,
-                           nb.pub ? (const unsigned char*)v.cls.d_pub : nullptr, nb.pub);
-    if (!carry) {
-        if (v.d_evid) HIP_TRY(hipMemsetAsync(v.d_evid, 0, 2 * ext_align(8 * (size_t)v.rec_cap), c->stream));
-        if (v.cls.d_pub) HIP_TRY(hipMemsetAsync(v.cls.d_pub, 0, (size_t)v.rec_cap, c->stream));
-    }
-    HIP_TRY(hipMemsetAsync(v.d_table, 0xff, 24 * (size_t)v.cap, c->stream));
-    HIP_TRY(hipMemsetAsync(v.d_table + 24 * (size_t)v.cap, 0, 4 * (size_t)v.cap, c->stream));
-    const long long nblocks = (M2 + BLOCK - 1) / BLOCK;
-    for (long long b0 = 0; b0 < nblocks; b0 += per)
-        hipLaunchKernelGGL(k_vret_table, dim3((unsigned)std::min(per, nblocks - b0)), dim3(BLOCK), 0, c->stream, (const float*)nr.xyz,
-                           M2, b0 * BLOCK, v.inv, v.tb, d_ctr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_tot + 8, d_ctr, 8, hipMemcpyDeviceToHost, c->stream));
-
-    // the log: the old pairs that stay, in log order, through remap into the emptied set, in place
-    unsigned long long* h_otot = nullptr;
-    if (E > 0) {
-        const size_t b4 = ext_align(4 * (size_t)v.rec_cap);
-        HIP_TRY(hipMemsetAsync(o.d_table, 0xff, 20 * (size_t)o.cap, c->stream));
-        HIP_TRY(hipMemsetAsync(o.d_ent, 0xff, b4, c->stream));
-        HIP_TRY(hipMemsetAsync(o.d_ent + b4, 0, b4, c->stream));
-        HIP_TRY(hipMemsetAsync(d_octr, 0, 24, c->stream));
-        for (long long b0 = 0; b0 < eblocks; b0 += per)
-            hipLaunchKernelGGL(k_vobs_import_insert, dim3((unsigned)std::min(per, eblocks - b0)), dim3(BLOCK), 0, c->stream,
-                               (const unsigned*)o.log.entry, (const int*)o.log.tag, (const unsigned*)d_remap, M, E, b0 * BLOCK,
-                               (unsigned)M2, o.tb, d_owhere, d_octr, (const unsigned char*)d_pmark);
-        for (long long t0 = 0; t0 < ot; t0 += per)
-            hipLaunchKernelGGL(k_vobs_count, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, d_owhere, E, t0,
-                               d_ocnt);
-        hipLaunchKernelGGL(k_extract_scan_tiles, dim3((unsigned)ob), dim3(BLOCK), 0, c->stream, d_ocnt, ot, d_ooff, d_obsum);
-        hipLaunchKernelGGL(k_extract_scan_sums, dim3(1), dim3(BLOCK), 0, c->stream, d_obsum, (int)ob, d_oboff);
-        hipLaunchKernelGGL(k_vobs_totals, dim3(1), dim3(64), 0, c->stream, ot, d_ooff, d_oboff, d_octr, d_otot);
-        for (long long t0 = 0; t0 < ot; t0 += per)
-            hipLaunchKernelGGL(k_vobs_commit, dim3((unsigned)std::min(per, ot - t0)), dim3(BLOCK), 0, c->stream, o.tb, o.log,
-                               o.last_obs, o.ncam, d_owhere, 0u, E, t0, d_ooff, d_oboff);
-        HIP_TRY(hipGetLastError());
-        h_otot = reinterpret_cast<unsigned long long*>(o.h_pin);
-        HIP_TRY(hipMemcpyAsync(h_otot, d_otot, 32, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end
-    if (reinterpret_cast<unsigned*>(h_tot + 8)[1]) return fail(SDM_EHIP, "voxel map table overflow");
-    if (h_otot && h_otot[3]) return fail(SDM_EHIP, "observation set overflow");
-
-    // the second sets become the map's; the old ones go with `nb`
-    std::swap(v.d_rec, nb.rec);
-    v.rec = nr;
-    if (nb.evid) {
-        std::swap(v.d_evid, nb.evid);
-        v.crossings = ncr;
-        v.ends = nen;
-    }
-    if (nb.pub) std::swap(v.cls.d_pub, nb.pub);
-    v.cls.published = delta->published_total;
-    v.M = M2;
-    v.calls++;
-    if (h_otot) o.E = (long long)h_otot[0];
-    return SDM_OK;
-}
+// ---- the persistent voxel map: every sdm_vmap_* call and the steps they share ---------------------------------------------
+#include "sdm_vmap_host.h"
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
 

@@ -550,3 +550,50 @@ def test_determinism_and_no_side_effects(pkg, gpu_ok):
     eng.vmap_close()  # the second engine's map is freed by sdm_destroy
     for e in engs:
         e.close()
+
+
+# 9. growth with every optional per-entry array present: what the old entries hold is carried over bit for bit, the new
+# entries start empty
+def test_growth_carries_every_array(engines):
+    g, eng = engines("plane_64x48_n7")
+    voxel, kw = 0.02, dict(max_sigma=0.3)
+    slots, nbrs = [0, 1], np.ascontiguousarray(g["nbrs"][:2, :3])
+
+    def everything(m):
+        got = dict(eng.vmap_fetch(first=0, count=m))
+        got.update(eng.vmap_fetch_evidence(first=0, count=m))
+        got.update(eng.vmap_fetch_cameras(first=0, count=m))
+        got["published"] = eng.vmap_fetch_published(first=0, count=m)
+        return {f: np.array(a) for f, a in got.items()}
+
+    eng.vmap_open(voxel, 0)
+    try:
+        T = eng.vmap_integrate(slots, updated=False, **kw)["plain_total"]
+        eng.vmap_carve(slots, nbrs, **kw)
+        eng.vmap_observe(slots, nbrs, **kw)
+        assert eng.vmap_classify(dict(min_multiplicity=1), commit=True, ids=False)["accepted"] > 0
+        info = eng.vmap_info()
+        M0, r0 = info["voxels"], info["rehashes"]
+        before = everything(M0)
+        assert M0 > 100 and before["crossings"].any() and before["ends"].any()
+        assert len(before["cam_tags"]) >= M0 and before["published"].any()
+        # records at fresh voxels, far from the scene, until the table has rehashed and the records have outgrown both
+        # 2 * M0 and the capacity the integrate left (its plain points)
+        n = 0
+        while info["rehashes"] == r0 or info["voxels"] <= max(2 * M0, T):
+            i = np.arange(n, n + 1500)
+            n += 1500
+            xyz = ((np.stack([i % 64, i // 64, np.full(len(i), 5000)], axis=1) + 0.5) * voxel).astype(np.float32)
+            d = eng.vmap_import({"xyz": xyz, "rho_sigma": np.full((len(i), 2), 0.5, np.float32)}, dst_ids=False, updated=False)
+            assert d["created"] == len(i)
+            info = eng.vmap_info()
+        M = info["voxels"]
+        assert M == M0 + n
+        after = everything(M)
+        for f in before:
+            m = before["cam_offsets"][-1] if f == "cam_tags" else len(before[f])
+            assert after[f][:m].tobytes() == before[f].tobytes(), f
+        assert not after["crossings"][M0:].any() and not after["ends"][M0:].any() and not after["published"][M0:].any()
+        assert (after["cam_offsets"][M0:] == before["cam_offsets"][-1]).all() and len(after["cam_tags"]) == len(before["cam_tags"])
+    finally:
+        eng.vmap_close()
