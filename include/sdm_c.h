@@ -611,7 +611,8 @@ int sdm_vmap_fetch(sdm_ctx *ctx, const unsigned *ids /*[count] or NULL*/, long l
  * stale with sdm_set_pose, as the stored xyz do; a keyframe's contribution cannot be removed from the counters
  * (sdm_vmap_retire, below, removes its entries and pairs, and its carry = 1 keeps the rays it added); one rank only: the
  * counters do not travel with sdm_vmap_import (below) -- carve on the merged map.  sdm_vmap_repose (below) carries or
- * restarts the counters when the poses move. */
+ * restarts the counters when the poses move, and sdm_vmap_recarve (further below) makes them again from the observation
+ * log when the slots that made them are gone. */
 typedef struct {
     int end_margin;            /* in: >= 0 */
     int max_steps;             /* in: 1 .. SDM_FREESPACE_MAX_STEPS */
@@ -981,7 +982,8 @@ int sdm_vmap_import_observations(sdm_ctx *ctx, long long count, sdm_vmap_obs_imp
  * of counters and flags (17 B per record of capacity); the old sets are freed before the call returns.  The log and the
  * set are rebuilt in their own storage with 4 B per old pair of scratch.
  * Limits: only each voxel's winning point is re-placed -- the points that lost are gone, so a reposed map is not the map
- * of integrating everything again under the new poses; carried evidence belongs to rays walked under the old poses; two
+ * of integrating everything again under the new poses; carried evidence belongs to rays walked under the old poses
+ * (sdm_vmap_recarve, further below, walks the log's rays again under the new ones); two
  * successive reposes are not one repose with the union table (entries merged by the first stay merged); ids and log
  * indices change and remap is the consumer's only bridge; one rank only per map. */
 typedef struct {
@@ -1056,7 +1058,8 @@ int sdm_vmap_repose(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses]*/, co
  * Limits: the points that lost are gone -- a map after WINNER-retiring R is a subset of the map of integrating only the
  * other keyframes, not equal to it; the multiplicity is NOT reduced, because the map does not know which keyframe added
  * what; carried counters still contain the rays of retired keyframes; ids and log indices change and remap is the
- * consumer's only bridge; one rank only per map; rebuilding evidence from the log's pairs is not part of this. */
+ * consumer's only bridge; one rank only per map; the evidence without the retired rays is rebuilt from the log's pairs by
+ * sdm_vmap_recarve (next). */
 #define SDM_VMAP_RETIRE_WINNER 0
 #define SDM_VMAP_RETIRE_UNOBSERVED 1
 typedef struct {
@@ -1080,6 +1083,68 @@ typedef struct {
     long long published_total;     /* after the call */
 } sdm_vmap_retire_delta;
 int sdm_vmap_retire(sdm_ctx *ctx, int n_tags, const int *tags /*[n_tags], host*/, int commit, sdm_vmap_retire_delta *delta);
+/* Rebuilding the free-space evidence from the observation log: sdm_vmap_carve reads the resident slots of a block, so once
+ * a repose has restarted (or carried) the counters, or a retire has kept the rays of retired keyframes in them, the evidence
+ * of everything older than the last block could not be made again.  The map holds what that takes: the log's (entry, tag)
+ * pairs are the rays, the entry's record holds the end point -- already re-placed by a repose -- and the caller holds the
+ * poses, the table it hands to the repose.  sdm_vmap_recarve walks one ray per pair of the log through the map's table on
+ * the device and adds to the per-entry counters.  It closes the online recipe: repose, (retire,) recarve, classify.  The
+ * semantics are this library's (tests/vmap_recarve_np.py restates them with tests/vmap_carve_np.py's walker).  Requires an
+ * open map.  tags[n_poses] and Tcw[n_poses][12] are host arrays; the log's pairs are k = 0 .. E-1.
+ *   - Rays: pair k of the range first .. first + count - 1 (count == -1: to the end of the log) is (e, t) = (obs_entry[k],
+ *     obs_tag[k]).  If t is not in tags, the pair adds 1 to pairs_unposed and nothing else.  Otherwise it is one ray from O
+ *     to P: O is the camera centre of Tcw[p], tags[p] == t, formed on the host exactly as
+ *     sdm_extract_points_voxel_freespace forms it -- Rwc[i][j] = Tcw[j*4+i], Ow_i = (Rwc[i][0]*t0 + Rwc[i][1]*t1) +
+ *     Rwc[i][2]*t2, O = -Ow (tests/carve_np.camera_centre) -- and P is the xyz of record e as it stands now.
+ *   - Walk: the skip rule, the cells, the integer-driven walk of exactly N steps, the tie rule and the counted cells
+ *     s <= N - 1 - end_margin are sdm_extract_points_voxel_freespace's and sdm_vmap_carve's, word for word, with the map's
+ *     voxel_size and inv; IEEE binary32, no FMA, the plain division.  A non-finite pose is not an error: its rays are
+ *     skipped (rays_skipped), as is a ray with a cell outside [-2^20, 2^20) or with N > max_steps.
+ *   - Counting: every counted cell whose key has an entry adds 1 to crossings[id]; the end cell is probed once and its
+ *     entry gets 1 on ends[id], whatever end_margin.
+ *   - State: the map, the log, the flags and every info struct are left as they are.  The counters are allocated and
+ *     zeroed if no carve has run yet (the allocation of the first sdm_vmap_carve; it grows with the records as before).
+ *     With reset == 1 both counters of all M entries are put to 0 before anything is added, also when the range or the
+ *     table is empty; with reset == 0 the call adds to what is there.  No log (E == 0) is not an error: zero pairs.
+ *   - Outs: pairs_total = pairs examined; pairs_unposed; rays_total = pairs_total - pairs_unposed; rays_skipped;
+ *     cells_visited = counted (ray, cell) pairs; cells_hit = the sum of the crossings added; ends_hit = the sum of the
+ *     ends added.
+ * Consequences: with reset == 1 over the whole log the counters are a pure function of (records, log, table), bitwise --
+ * unlike sdm_vmap_carve, whose evidence depends on which entries existed at each call.  The call is additive over any
+ * split of the log range into calls with reset == 0.  P lies in its own entry's voxel, so every walked ray ends in an
+ * entry: ends_hit == rays_total - rays_skipped, and ends[e] is the number of walked pairs of entry e.  Everything is an
+ * integer sum: bitwise the same from run to run, whatever the table layout.
+ * Errors, all raised before any counter changes; none depends on device data:
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: a NULL ctx or rc; n_poses < 0; a NULL tags or Tcw with n_poses > 0; a tag outside [0, 2^31); a tag listed
+ *     twice; end_margin < 0; max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS; reset not 0 or 1; first < 0, count < -1 or
+ *     first + count > E.
+ *   SDM_EHIP: an allocation failure -- everything is allocated before anything is written.
+ * On a refusal the outs are 0.
+ * Cost: the table of (tag, centre) is sorted by tag on the host and uploaded once, 20 B per pose.  One lane per pair: 8 B
+ * of the log read and one binary search; a posed lane reads 12 B of the record's xyz and walks as sdm_vmap_carve does --
+ * six float divisions, per counted cell one read-only probe of the table (on a hit one 64-bit atomic add), one probe for
+ * the end cell.  With reset one memset over the counters.  One host wait: the end, with the totals; nothing but the table
+ * and 48 B of totals crosses the link.  Log order is point-major, so a wave mixes cameras (a tag-sorted order has not been
+ * measured).  Measured: DESIGN.md s.25.  Memory: 16 B per record of capacity if no carve has run, 20 B per pose of scratch.
+ * Limits: one ray per distinct (entry, tag), not one per plain point as in sdm_vmap_carve -- the two agree only where
+ * every multiplicity is 1; the ray ends at the voxel's WINNING point, not at each point the camera saw there; one rank
+ * only (the counters do not travel: recarve on the merged map); recarving a range twice without reset counts twice. */
+typedef struct {
+    int end_margin;            /* in: >= 0 */
+    int max_steps;             /* in: 1 .. SDM_FREESPACE_MAX_STEPS */
+    int reset;                 /* in: 1: both counters of EVERY entry are set to 0 first; 0: the call adds to them */
+    long long first, count;    /* in: the log pairs first .. first+count-1; count == -1: from first to the end of the log */
+    long long pairs_total;     /* out: pairs examined */
+    long long pairs_unposed;   /* out: of those, pairs whose tag is not in the table (no ray) */
+    long long rays_total;      /* out: pairs_total - pairs_unposed */
+    long long rays_skipped;    /* out */
+    long long cells_visited;   /* out */
+    long long cells_hit;       /* out: = sum of the crossings added */
+    long long ends_hit;        /* out: = sum of the ends added */
+} sdm_vmap_recarve_args;
+int sdm_vmap_recarve(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses], host*/,
+                     const float *Tcw /*[n_poses][12], host*/, sdm_vmap_recarve_args *rc);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -168,6 +168,14 @@ class VmapRetireDelta(C.Structure):
                 ("published_total", C.c_longlong)]
 
 
+class VmapRecarveArgs(C.Structure):
+    """sdm_vmap_recarve_args"""
+    _fields_ = [("end_margin", C.c_int), ("max_steps", C.c_int), ("reset", C.c_int), ("first", C.c_longlong),
+                ("count", C.c_longlong), ("pairs_total", C.c_longlong), ("pairs_unposed", C.c_longlong),
+                ("rays_total", C.c_longlong), ("rays_skipped", C.c_longlong), ("cells_visited", C.c_longlong),
+                ("cells_hit", C.c_longlong), ("ends_hit", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -207,6 +215,8 @@ VMAP_RETIRE_LISTS = {"remap": (np.uint32, "remap_capacity", "examined"),
                      "dropped_published": (np.uint8, "dropped_capacity", "dropped"),
                      "removed_entry": (np.uint32, "removed_capacity", "removed"),
                      "removed_tag": (np.int32, "removed_capacity", "removed")}
+# the outs of sdm_vmap_recarve
+VMAP_RECARVE_OUTS = ("pairs_total", "pairs_unposed", "rays_total", "rays_skipped", "cells_visited", "cells_hit", "ends_hit")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -287,6 +297,7 @@ SYMBOLS = [
     ("sdm_vmap_import_observations", C.c_int, [_ctx, C.c_longlong, C.POINTER(VmapObsImport)]),
     ("sdm_vmap_repose", C.c_int, [_ctx, C.c_int, _ip, _f32p, _f32p, C.POINTER(VmapReposeDelta)]),
     ("sdm_vmap_retire", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.POINTER(VmapRetireDelta)]),
+    ("sdm_vmap_recarve", C.c_int, [_ctx, C.c_int, _ip, _f32p, C.POINTER(VmapRecarveArgs)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1570,6 +1581,28 @@ class Engine:
         for f, a in dests.items():
             res[f] = a[:res[VMAP_RETIRE_LISTS[f][2]]]
         return res
+
+    def vmap_recarve(self, tags, Tcw, end_margin=1, max_steps=4096, reset=True, first=0, count=None):
+        """Rebuilds the voxel map's free-space evidence from its observation log (sdm_vmap_recarve): one ray per log pair
+        (entry, tag) of the range first .. first + count - 1 (count None: to the end of the log), from the camera centre
+        of Tcw[p], tags[p] == tag, to the xyz in the entry's record, walked through the map as vmap_carve walks.  tags
+        int32[n] and Tcw float32[n, 12]; a pair whose tag is not in tags makes no ray.  reset True puts both counters of
+        every entry to 0 first; False adds to them.  The map, the log and the flags are only read: after vmap_repose
+        (and vmap_retire) call this with the same table, then vmap_classify.  Returns {"pairs_total", "pairs_unposed",
+        "rays_total", "rays_skipped", "cells_visited", "cells_hit", "ends_hit"}."""
+        tg = np.ascontiguousarray(np.asarray([] if tags is None else tags, dtype=np.int32).reshape(-1))
+        n = len(tg)
+        tp = pp = None
+        if n:
+            t12, pp = _f32(np.asarray(Tcw, dtype=np.float32).reshape(-1, 12))
+            if len(t12) != n:
+                raise ValueError("Tcw: need one row per tag")
+            tp = tg.ctypes.data_as(_ip)
+        rc = VmapRecarveArgs()
+        rc.end_margin, rc.max_steps, rc.reset = int(end_margin), int(max_steps), int(reset)
+        rc.first, rc.count = int(first), -1 if count is None else int(count)
+        self._check(self.lib.sdm_vmap_recarve(self.ctx, n, tp, pp, C.byref(rc)))
+        return {f: int(getattr(rc, f)) for f in VMAP_RECARVE_OUTS}
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""

@@ -42,6 +42,8 @@
 #include "sdm_vmap_import.h"
 #include "sdm_vmap_repose.h"
 #include "sdm_vmap_retire.h"
+#include "sdm_vmap_recarve.h"
+#include "sdm_vmap_poses.h"
 
 using namespace sdm;
 

@@ -1955,3 +1955,82 @@ int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vma
     if (h_otot) o.E = (long long)h_otot[0];
     return SDM_OK;
 }
+
+// ---- rebuilding the free-space evidence from the observation log (sdm_vmap_recarve.h) -------------------------------------
+int sdm_vmap_recarve(sdm_ctx* c, int n_poses, const int* tags, const float* Tcw, sdm_vmap_recarve_args* rc)
+{
+    if (rc)
+        rc->pairs_total = rc->pairs_unposed = rc->rays_total = rc->rays_skipped = rc->cells_visited = rc->cells_hit = rc->ends_hit = 0;
+    if (!c || !rc) return fail(SDM_EINVAL, "null argument");
+    sdm_ctx::Vmap& v = c->vmap;
+    sdm_ctx::Vmap::Obs& o = v.obs;
+    if (!v.open) return fail(SDM_ESTATE, "no open voxel map");
+    std::vector<int> order;  // the table's rows by ascending tag
+    std::string why;
+    long long count = 0;
+    int r = recarve_check(n_poses, tags, Tcw, rc, o.E, &count, &order, &why);
+    if (r) return fail(r, why);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+
+    // the scratch, the pinned mirror and the counters: everything is allocated before anything is written
+    const size_t np = (size_t)n_poses;
+    const size_t tags_b = ext_align(4 * np), org_b = ext_align(16 * np);
+    ScratchHead head;  // tot: the kernel's six totals
+    int* d_tags = nullptr;
+    float* d_org = nullptr;
+    if ((r = carve_scratch(&v.d_scratch, &v.scratch_bytes, [&](Carver& k) {
+             head = ScratchHead(k);
+             d_tags = k.take<int>(np);  // (tags | centres: one copy fills both)
+             d_org = k.take<float>(4 * np);
+         })))
+        return r;
+    if ((r = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tags_b + org_b))) return r;
+    if (!v.d_evid) {  // (the allocation of the first sdm_vmap_carve)
+        DevBlock evid;
+        unsigned long long *cr = nullptr, *en = nullptr;
+        if ((r = vmap_make_evidence(c, v.rec_cap, evid, &cr, &en))) return r;
+        evid.install(v.d_evid);
+        v.crossings = cr, v.ends = en;
+    }
+    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
+    int* h_tags = reinterpret_cast<int*>(v.h_pin + 256);
+    float* h_org = reinterpret_cast<float*>(v.h_pin + 256 + tags_b);
+    for (size_t q = 0; q < np; q++) {
+        const size_t at = (size_t)order[q];
+        h_tags[q] = tags[at];
+        pose_centre(Tcw + 12 * at, h_org + 4 * q);
+        h_org[4 * q + 3] = 0.f;
+    }
+
+    if (rc->reset) HIP_TRY(vmap_zero_evidence(c, v.crossings, v.ends));
+    HIP_TRY(hipMemsetAsync(head.tot, 0, 64, c->stream));
+    if (np) HIP_TRY(stage_in(c, d_tags, h_tags, tags_b + org_b));
+    VmapRecarveIn in;
+    in.obs_entry = o.log.entry;
+    in.obs_tag = o.log.tag;
+    in.xyz = v.rec.xyz;
+    in.tags = d_tags;
+    in.origin = d_org;
+    in.first = rc->first;
+    in.count = count;
+    in.n = n_poses;
+    in.M = (unsigned)v.M;
+    in.voxel = v.voxel_size;
+    in.inv = v.inv;
+    in.end_margin = rc->end_margin;
+    in.max_steps = rc->max_steps;
+    launch_sliced((count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+        hipLaunchKernelGGL(k_vmap_recarve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, v.tb, v.crossings, v.ends, head.tot);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_tot, head.tot, 48, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the one wait: the end, with the totals
+    rc->pairs_total = (long long)h_tot[0];
+    rc->pairs_unposed = (long long)h_tot[1];
+    rc->rays_total = rc->pairs_total - rc->pairs_unposed;
+    rc->rays_skipped = (long long)h_tot[2];
+    rc->cells_visited = (long long)h_tot[3];
+    rc->cells_hit = (long long)h_tot[4];
+    rc->ends_hit = (long long)h_tot[5];
+    return SDM_OK;
+}
