@@ -1283,6 +1283,11 @@ int sdm_get_stats(sdm_ctx *ctx, sdm_stats *out, int reset);
  * wave and neighbour, from the wave's range lengths and line slopes; 1: always the batched scan; 2: always the scan over the
  * neighbour's gradient-gate bit plane.  Results are the same bit for bit in every mode (tests/test_gpu_longscan.py). */
 int sdm_set_scan_mode(sdm_ctx *ctx, int mode);
+/* Every launch whose grid grows with data goes out in groups of dispatches of at most 2^31 work-items (a test lowers the limit
+ * per context: SDM_MAX_DISPATCH_LOG2 in [8, 31], read by sdm_create).  What this context issued since the last reset, counted
+ * on the host (nothing is read from the device, nothing waits; sdm_stats does not move): out[0] = groups, out[1] = dispatches,
+ * out[2] = groups that took more than one dispatch.  With the default limit out[2] stays 0 below 2^31 work-items per launch. */
+int sdm_get_dispatch_counts(sdm_ctx *ctx, long long out[3], int reset);
 /* Streaming ingest (default off).  On: the batched uploads (sdm_upload_images_batch / _rgb_batch) get twelve chunk buffers
  * instead of four, so the host staging and the H2D copies (upload stream) of up to three 64-keyframe blocks run ahead of
  * their pre-pass kernels, which stay on the compute stream in call order (and, the copies being ahead anyway, run as ONE

@@ -336,6 +336,7 @@ SYMBOLS = [
     ("sdm_enable_stats", C.c_int, [_ctx, C.c_int]),
     ("sdm_get_stats", C.c_int, [_ctx, C.POINTER(Stats), C.c_int]),
     ("sdm_set_scan_mode", C.c_int, [_ctx, C.c_int]),
+    ("sdm_get_dispatch_counts", C.c_int, [_ctx, C.POINTER(C.c_longlong), C.c_int]),
     ("sdm_get_params", C.c_int, [_ctx, C.POINTER(Params)]),
     ("sdm_set_ingest_overlap", C.c_int, [_ctx, C.c_int]),
     ("sdm_selftest", C.c_int, [_ctx, C.c_int, C.POINTER(C.c_ulonglong)]),
@@ -1786,6 +1787,12 @@ class Engine:
     def set_scan_mode(self, mode):
         """0 = per wave (default), 1 = batched scan, 2 = gradient-mask scan (diagnostic; results are identical)"""
         self._check(self.lib.sdm_set_scan_mode(self.ctx, int(mode)))
+
+    def dispatch_counts(self, reset=False):
+        """(groups of sliced launches, dispatches, groups of more than one dispatch) since the last reset; host-side"""
+        out = (C.c_longlong * 3)()
+        self._check(self.lib.sdm_get_dispatch_counts(self.ctx, out, 1 if reset else 0))
+        return tuple(int(v) for v in out)
 
     def enable_stats(self, on=True):
         self._check(self.lib.sdm_enable_stats(self.ctx, 1 if on else 0))

@@ -150,6 +150,11 @@ struct sdm_ctx {
     int mrow = 0;                              // 32-bit words per image row: 2 * (tiles_x + 1) (the last two stay zero: the scan
                                                // reads the word after the one a column lies in)
     int scan_mode = 0;                         // DevParams::scan_mode (SDM_SCAN_MODE, read once in sdm_create)
+    // work-items one dispatch may hold (for_ref_slices / launch_sliced), read once in sdm_create: SDM_MAX_DISPATCH_LOG2 in
+    // [8, 31], or SDM_MAX_DISPATCH_ITEMS in [2^8, 2^31] where a test needs a split no power of two gives; and what the two
+    // helpers issued since the last reset (host-side only: sdm_get_dispatch_counts)
+    long long max_dispatch = 1ll << 31;
+    long long disp_groups = 0, disp_launches = 0, disp_multi = 0;
     // ---- streaming ingest (sdm_set_ingest_overlap): with twelve chunk buffers instead of four, the host staging and the H2D
     // copies of a batch upload (upload stream) run ahead of the pre-pass kernels (compute stream, in call order) by up to
     // three 64-keyframe blocks: a block uploaded BEFORE the previous block's step is queued is copied while that step runs
@@ -627,35 +632,47 @@ size_t select_set(sdm_ctx* c, int si, int n_ref, size_t np)
 // -- every keyframe's list positions below 108 032 -- and the rest of every map kept what it held before
 // (tools/debug/unsliced_holes.py).  Every launch whose grid grows with the number of reference keyframes is therefore issued
 // in slices of reference keyframes: fn(first, count) launches one slice.
-// (SDM_MAX_DISPATCH_LOG2: debugging knob, read once per process; values above 31 -- how the finding was reproduced --
-// need a build with -DSDM_DEBUG_KNOBS: tools/debug/unsliced_*.py.)
-template <typename F>
-void for_ref_slices(int n_ref, long long blocks_per_ref, int threads, F&& fn)
+// The limit is the context's (sdm_ctx::max_dispatch, 2^31 unless SDM_MAX_DISPATCH_LOG2 / SDM_MAX_DISPATCH_ITEMS said otherwise
+// when the context was created), so a test runs an engine that slices at 2^8 .. 2^10 work-items beside a default one
+// (tests/test_gpu_slices.py): the slice offsets of every call site below and in sdm_vmap_host.h, and what a call carries
+// from one slice to the next (open list, grow list, per-call counters, scans, totals), are verified that way at test sizes.
+// NOT verified by that: index width beyond 2^31 work-items (test_gpu_fullsize.py reaches for_ref_slices only) and the
+// 2^30 / 2^40 refusals.  A limit below a launch's workgroup size gives one workgroup (one reference) per dispatch.
+// Values above 2^31 -- how the finding was reproduced -- need a build with -DSDM_DEBUG_KNOBS; such a build also reads
+// SDM_MAX_DISPATCH_LOG2 again at every launch, since tools/debug/unsliced_*.py switch it between the calls of one engine.
+// Every group of dispatches is counted on the host (sdm_get_dispatch_counts).
+inline long long dispatch_limit(const sdm_ctx* c)
 {
-    // read once; above 31 only in SDM_DEBUG_KNOBS builds (beyond 2^32 work-items the launch silently runs a partial grid)
-    static const int lg = [] {
-        int v = 31;
-        if (const char* e = getenv("SDM_MAX_DISPATCH_LOG2")) {
 #ifdef SDM_DEBUG_KNOBS
-            v = std::max(20, std::min(40, atoi(e)));
-#else
-            v = std::max(20, std::min(31, atoi(e)));
+    if (const char* e = getenv("SDM_MAX_DISPATCH_LOG2")) return 1ll << std::max(8, std::min(40, atoi(e)));
 #endif
-        }
-        return v;
-    }();
-    const long long max_blocks = (1ll << lg) / threads;
+    return c->max_dispatch;
+}
+inline void count_dispatches(sdm_ctx* c, long long dispatches)
+{
+    c->disp_groups++;
+    c->disp_launches += dispatches;
+    if (dispatches > 1) c->disp_multi++;
+}
+template <typename F>
+void for_ref_slices(sdm_ctx* c, int n_ref, long long blocks_per_ref, int threads, F&& fn)
+{
+    const long long max_blocks = std::max<long long>(1, dispatch_limit(c) / threads);
     const int per = (int)std::max<long long>(1, std::min<long long>(n_ref, max_blocks / std::max<long long>(blocks_per_ref, 1)));
-    for (int first = 0; first < n_ref; first += per) fn(first, std::min(per, n_ref - first));
+    long long dispatches = 0;
+    for (int first = 0; first < n_ref; first += per, dispatches++) fn(first, std::min(per, n_ref - first));
+    count_dispatches(c, dispatches);
 }
 
 // The same limit (the comment above for_ref_slices) for a grid that grows with points, tiles or table slots: `blocks`
-// workgroups of `threads` work-items go out in dispatches of at most 2^31 work-items, fn(first_block, grid) launches one.
+// workgroups of `threads` work-items go out in dispatches of at most max_dispatch work-items, fn(first_block, grid) launches one.
 template <typename F>
-void launch_sliced(long long blocks, F&& fn, int threads = BLOCK)
+void launch_sliced(sdm_ctx* c, long long blocks, F&& fn, int threads = BLOCK)
 {
-    const long long per = (1ll << 31) / threads;
-    for (long long b0 = 0; b0 < blocks; b0 += per) fn(b0, (unsigned)std::min(per, blocks - b0));
+    const long long per = std::max<long long>(1, std::min(dispatch_limit(c), 1ll << 31) / threads);  // (the grid is 32 bits wide)
+    long long dispatches = 0;
+    for (long long b0 = 0; b0 < blocks; b0 += per, dispatches++) fn(b0, (unsigned)std::min(per, blocks - b0));
+    count_dispatches(c, dispatches);
 }
 
 // workgroups of k_extract_scan_tiles over the tiles + 1 offsets of `tiles` per-tile counts: what bsum and boff hold
@@ -1086,6 +1103,16 @@ int sdm_create(sdm_ctx** out, const sdm_config* cfg)
         c->mrow = 2 * (c->geom.tiles_x + 1);
         if ((rc = dev_alloc(&c->d_gmask, (size_t)K * c->H * MASK_PLANES * c->mrow))) return bail(rc);
         if (const char* e = getenv("SDM_SCAN_MODE")) c->scan_mode = std::max(0, std::min(2, atoi(e)));  // tests / A-B
+        // tests: launches go out in slices this small (above 2^31 only in SDM_DEBUG_KNOBS builds: beyond 2^32 work-items a
+        // launch silently runs a partial grid)
+#ifdef SDM_DEBUG_KNOBS
+        const int lg_max = 40;
+#else
+        const int lg_max = 31;
+#endif
+        if (const char* e = getenv("SDM_MAX_DISPATCH_LOG2")) c->max_dispatch = 1ll << std::max(8, std::min(lg_max, atoi(e)));
+        if (const char* e = getenv("SDM_MAX_DISPATCH_ITEMS"))
+            c->max_dispatch = std::max<long long>(1ll << 8, std::min<long long>(1ll << lg_max, atoll(e)));
         set_dev_params(c);
     }
     if ((rc = dev_alloc(&c->d_im, (size_t)c->P))) return bail(rc);
@@ -1714,7 +1741,7 @@ static int launch_search_fuse(sdm_ctx* c, int n_ref, int n, const int* ref_slots
     // K1 writes every listed pixel; the rest of the map must be zero (a fresh depth_map_).  It already is
     // when the slot's current map came out of SemiDenseRecon under the same lambdaG.
     if (!all_pipeline_maps(c, n_ref, ref_slots)) {
-        for_ref_slices(n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
+        for_ref_slices(c, n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
             hipLaunchKernelGGL(k_zero_maps, dim3(blocks_for(c->P * count)), dim3(BLOCK), 0, c->stream, c->pool, c->P,
                                c->d_ref_slots + first, count);
         });
@@ -1745,7 +1772,7 @@ static int launch_search_fuse(sdm_ctx* c, int n_ref, int n, const int* ref_slots
     const bool mask = c->scan_mode == 2 || (c->scan_mode == 0 && c->sets[c->cur_set].key.long_ranges);
     auto k1 = c->stats_on ? (mask ? k_search_fuse<true, true> : k_search_fuse<true, false>)
                           : (mask ? k_search_fuse<false, true> : k_search_fuse<false, false>);
-    for_ref_slices(n_ref, blocks_per_ref, K1_BLOCK, [&](int first, int count) {
+    for_ref_slices(c, n_ref, blocks_per_ref, K1_BLOCK, [&](int first, int count) {
         hipLaunchKernelGGL(k1, dim3(blocks_per_ref * count), dim3(K1_BLOCK), lds, c->stream, c->rec, c->P, c->d_refs + first,
                            c->d_pairs + (size_t)first * n, count, n, c->W, c->H, max_chunks, c->dprm, c->d_act, c->pool, c->d_stats,
                            ol, c->d_gmask, c->mrow);
@@ -1810,14 +1837,14 @@ static int launch_intra(sdm_ctx* c, int n_ref, int first, int count, bool check,
     // offsets: [0..K) pool offsets, [K..2K) scratch offsets, [2K..3K) record offsets (in floats)
     const int K = n_ref;  // offset tables are [3][n_ref]
     if (check) {
-        for_ref_slices(count, grid_blocks(c->geom, 1), BLOCK, [&](int f, int cn) {
+        for_ref_slices(c, count, grid_blocks(c->geom, 1), BLOCK, [&](int f, int cn) {
             hipLaunchKernelGGL(k_intra_check, dim3(grid_blocks(c->geom, cn)), dim3(BLOCK), 0, c->stream, c->pool, c->scratch,
                                c->d_off + first + f, c->d_off + K + first + f, cn, c->geom);
         });
         HIP_TRY(hipGetLastError());
     }
     if (grow) {
-        for_ref_slices(count, grid_blocks(c->geom, 1), BLOCK, [&](int f, int cn) {
+        for_ref_slices(c, count, grid_blocks(c->geom, 1), BLOCK, [&](int f, int cn) {
             hipLaunchKernelGGL(k_intra_grow, dim3(grid_blocks(c->geom, cn)), dim3(BLOCK), 0, c->stream, c->scratch, c->pool,
                                c->d_off + K + first + f, c->d_off + first + f, (const float*)c->rec,
                                c->d_off + 2 * K + first + f, 4, cn, c->geom, c->dprm.lambdaG);
@@ -1850,7 +1877,7 @@ static int run_intra_lists(sdm_ctx* c, int n_ref, const int* ref_slots, bool che
         gl.capacity = c->grow_capacity;
         gl.pix = c->d_grow_pix;
         gl.val = c->d_grow_val;
-        for_ref_slices(count, per_ref, BLOCK, [&](int f, int cn) {
+        for_ref_slices(c, count, per_ref, BLOCK, [&](int f, int cn) {
             if (check && grow)
                 hipLaunchKernelGGL((k_intra_compact<true, true>), dim3(per_ref * cn), dim3(BLOCK), 0, c->stream, c->pool,
                                    c->scratch, c->d_off, c->d_off + K, c->d_refs, first + f, cn, c->W, max_chunks, c->P,
@@ -1866,7 +1893,7 @@ static int run_intra_lists(sdm_ctx* c, int n_ref, const int* ref_slots, bool che
         });
         HIP_TRY(hipGetLastError());
         if (check) {
-            for_ref_slices(count, per_ref, BLOCK, [&](int f, int cn) {
+            for_ref_slices(c, count, per_ref, BLOCK, [&](int f, int cn) {
                 hipLaunchKernelGGL(k_intra_commit, dim3(per_ref * cn), dim3(BLOCK), 0, c->stream, c->pool, c->scratch, c->d_off,
                                    c->d_off + K, c->d_refs, first + f, cn, c->W, max_chunks, c->P, c->d_act);
             });
@@ -1884,7 +1911,7 @@ static int run_intra_lists(sdm_ctx* c, int n_ref, const int* ref_slots, bool che
             // neighbours outside the list instead of reading them, so the planes need no clearing -- unless the
             // pass stands alone and the whole plane is copied back below
             if (!grow) HIP_TRY(hipMemsetAsync(c->scratch, 0, sizeof(float2) * c->P * count, c->stream));
-            for_ref_slices(count, per_ref, BLOCK, [&](int f, int cn) {
+            for_ref_slices(c, count, per_ref, BLOCK, [&](int f, int cn) {
                 hipLaunchKernelGGL(k_intra_list<false>, dim3(per_ref * cn), dim3(BLOCK), 0, c->stream, c->pool, c->scratch,
                                    c->d_off, c->d_off + K, c->d_refs, first + f, cn, c->W, max_chunks, c->P, c->d_act, c->rec,
                                    c->H, c->dprm.lambdaG);
@@ -1896,7 +1923,7 @@ static int run_intra_lists(sdm_ctx* c, int n_ref, const int* ref_slots, bool che
                                        sizeof(float2) * c->P, hipMemcpyDeviceToDevice, c->stream));
         }
         if (grow) {
-            for_ref_slices(count, per_ref, BLOCK, [&](int f, int cn) {
+            for_ref_slices(c, count, per_ref, BLOCK, [&](int f, int cn) {
                 hipLaunchKernelGGL(k_intra_list<true>, dim3(per_ref * cn), dim3(BLOCK), 0, c->stream, c->scratch, c->pool,
                                    c->d_off + K, c->d_off, c->d_refs, first + f, cn, c->W, max_chunks, c->P, c->d_act, c->rec,
                                    c->H, c->dprm.lambdaG);
@@ -2027,7 +2054,7 @@ static int inter_check_core(sdm_ctx* c, int n_ref, const int* ref_slots, int n, 
             bool chk_ok = true;  // checked planes already zero outside the lists?
             for (int r = 0; r < n_ref; r++) chk_ok = chk_ok && c->chk_sparse[ref_slots[r]];
             if (!chk_ok) {
-                for_ref_slices(n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
+                for_ref_slices(c, n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
                     hipLaunchKernelGGL(k_rho_copy, dim3(blocks_for(c->P * count)), dim3(BLOCK), 0, c->stream, c->pool, c->chk,
                                        c->P, c->d_ref_slots + first, count);
                 });
@@ -2040,7 +2067,7 @@ static int inter_check_core(sdm_ctx* c, int n_ref, const int* ref_slots, int n, 
             if (max_chunks > 0) {
                 max_chunks = (max_chunks * BLOCK + K4_BLOCK - 1) / K4_BLOCK;  // in units of the list kernel's workgroup
                 const int per_ref = band_grid_per_ref(max_chunks, SDM_K4_GROUP, SDM_K4_BAND);
-                for_ref_slices(n_ref, per_ref, K4_BLOCK, [&](int first, int count) {
+                for_ref_slices(c, n_ref, per_ref, K4_BLOCK, [&](int first, int count) {
                     const dim3 grid(per_ref * count);
                     if (fuse)
                         hipLaunchKernelGGL(k_inter_check_list<true>, grid, dim3(K4_BLOCK), c->k4_lds_pad, c->stream, c->pool, c->P,
@@ -2056,7 +2083,7 @@ static int inter_check_core(sdm_ctx* c, int n_ref, const int* ref_slots, int n, 
             *xyz_done = fuse;
         } else {
             for (int r = 0; r < n_ref; r++) c->chk_sparse[ref_slots[r]] = 0;  // the generic kernel copies arbitrary maps
-            for_ref_slices(n_ref, grid_blocks(c->geom, 1), BLOCK, [&](int first, int count) {
+            for_ref_slices(c, n_ref, grid_blocks(c->geom, 1), BLOCK, [&](int first, int count) {
                 hipLaunchKernelGGL(k_inter_check, dim3(grid_blocks(c->geom, count)), dim3(BLOCK), 0, c->stream, c->pool, c->P,
                                    c->d_refs + first, c->d_pairs + (size_t)first * n, count, n, c->geom, c->dprm.lambdaN,
                                    c->chk);
@@ -2064,7 +2091,7 @@ static int inter_check_core(sdm_ctx* c, int n_ref, const int* ref_slots, int n, 
             HIP_TRY(hipGetLastError());
         }
         if (commit) {
-            for_ref_slices(n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
+            for_ref_slices(c, n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
                 hipLaunchKernelGGL(k_commit, dim3(blocks_for(c->P * count)), dim3(BLOCK), 0, c->stream, c->chk, c->pool, c->P,
                                    c->d_ref_slots + first, count);
             });
@@ -2110,13 +2137,13 @@ int sdm_pointset(sdm_ctx* c, int n_ref, const int* ref_slots, int source)
     if (sparse) {
         if (max_chunks > 0) {
             const int per_ref = band_grid_per_ref(max_chunks, SDM_K23_GROUP, SDM_K23_BAND);
-            for_ref_slices(n_ref, per_ref, BLOCK, [&](int first, int count) {
+            for_ref_slices(c, n_ref, per_ref, BLOCK, [&](int first, int count) {
                 hipLaunchKernelGGL(k_pointset_list, dim3(per_ref * count), dim3(BLOCK), 0, c->stream, src, sstride, c->P,
                                    c->d_meta, c->d_refs + first, count, c->W, max_chunks, c->d_act, c->xyz);
             });
         }
     } else {
-        for_ref_slices(n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
+        for_ref_slices(c, n_ref, blocks_for(c->P), BLOCK, [&](int first, int count) {
             hipLaunchKernelGGL(k_pointset, dim3(blocks_for(c->P), count), dim3(BLOCK), 0, c->stream, src, sstride, c->P,
                                c->d_meta, c->d_ref_slots + first, count, c->W, c->H, c->xyz);
         });
@@ -2436,7 +2463,7 @@ static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const in
         }
         h_cut[n] = blocks;
         HIP_TRY(hipMemcpyAsync(d_cut, h_cut, sizeof(long long) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
-        launch_sliced(blocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, blocks, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_point_support, dim3(g), dim3(SUP_BLOCK), 0, c->stream, c->pool, c->P, c->d_refs, c->d_pairs, n,
                                n_nbr, c->W, c->H, d_cut, b0, d_offs, dst.pixel, d_sup);
         }, SUP_BLOCK);
@@ -2570,11 +2597,11 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
     HIP_TRY(hipMemsetAsync(tb.keys, 0xff, 2 * key_b, c->stream));  // keys: VOX_EMPTY; values: the minimum's identity
     HIP_TRY(hipMemsetAsync(tb.cnt, 0, cnt_b, c->stream));           // counts and the flag
     const long long pblocks = (T + BLOCK - 1) / BLOCK;
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_voxel_insert, dim3(g), dim3(BLOCK), 0, c->stream, st.at.xyz, st.at.rho_sigma, T, b0 * BLOCK, inv, tb,
                            d_where, d_flag);
     });
-    launch_sliced(vt, [&](long long t0, unsigned g) {
+    launch_sliced(c, vt, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_voxel_count, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0, d_tcnt);
     });
     scan_counts(c, d_tcnt, vt, d_toff, d_bsum, d_boff);
@@ -2702,19 +2729,19 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
             HIP_TRY(hipMemcpyAsync(d_org, c->h_vcam + 256 + ext_align(4 * cam_tab_n), 16 * (size_t)Cn, hipMemcpyHostToDevice,
                                    c->stream));
     }
-    launch_sliced(vt, [&](long long t0, unsigned g) {
+    launch_sliced(c, vt, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_voxel_write, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0, d_toff, d_boff, st.at, dst,
                            d_mult, d_sidx, d_rank);
     });
     if (d_rank)
-        launch_sliced(pblocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_voxel_rep, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, b0 * BLOCK, d_rank);
         });
     HIP_TRY(hipGetLastError());
     if (cams) {
         // SDM_VOXCAM_PLAIN_OR: one atomic per lane and word instead of one per run of equal rank (A/B; the same bits)
         const bool plain_or = getenv("SDM_VOXCAM_PLAIN_OR") != nullptr;
-        launch_sliced(st.blocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, st.blocks, [&](long long b0, unsigned g) {
             if (plain_or)
                 hipLaunchKernelGGL(k_voxcam_or<false>, dim3(g), dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
                                    st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
@@ -2722,7 +2749,7 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
                 hipLaunchKernelGGL(k_voxcam_or<true>, dim3(g), dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
                                    st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
         }, SUP_BLOCK);
-        launch_sliced(kt, [&](long long t0, unsigned g) {
+        launch_sliced(c, kt, [&](long long t0, unsigned g) {
             hipLaunchKernelGGL(k_voxcam_count, dim3(g), dim3(BLOCK), 0, c->stream, d_bits, Wd, M, t0, d_ktcnt);
         });
         scan_counts(c, d_ktcnt, kt, d_ktoff, d_kbsum, d_kboff);
@@ -2756,7 +2783,7 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
             else if (!out->on_device) d_cslots = nullptr;
             if (cross_b) d_cross = reinterpret_cast<unsigned*>(c->d_vcam_out + off_b + slots_b);
         }
-        launch_sliced(kt, [&](long long t0, unsigned g) {
+        launch_sliced(c, kt, [&](long long t0, unsigned g) {
             hipLaunchKernelGGL(k_voxcam_write, dim3(g), dim3(BLOCK), 0, c->stream, d_bits, Wd, M, t0, d_ktoff, d_kboff,
                                ctab.slot_of_cam, d_coff, d_cslots);
         });
@@ -2778,7 +2805,7 @@ static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int*
             in.end_margin = fs->end_margin;
             in.max_steps = fs->max_steps;
             const long long eblocks = (E + BLOCK - 1) / BLOCK;
-            launch_sliced(eblocks, [&](long long b0, unsigned g) {
+            launch_sliced(c, eblocks, [&](long long b0, unsigned g) {
                 hipLaunchKernelGGL(k_voxel_carve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, tb, d_cross, d_fs_tot);
             });
             HIP_TRY(hipGetLastError());
@@ -3462,6 +3489,16 @@ int sdm_set_scan_mode(sdm_ctx* c, int mode)
     if (mode < 0 || mode > 2) return fail(SDM_EINVAL, "scan mode must be 0, 1 or 2");
     c->scan_mode = mode;
     set_dev_params(c);
+    return SDM_OK;
+}
+
+int sdm_get_dispatch_counts(sdm_ctx* c, long long* out, int reset)
+{
+    if (!c || !out) return fail(SDM_EINVAL, "null argument");
+    out[0] = c->disp_groups;
+    out[1] = c->disp_launches;
+    out[2] = c->disp_multi;
+    if (reset) c->disp_groups = c->disp_launches = c->disp_multi = 0;
     return SDM_OK;
 }
 

@@ -333,7 +333,7 @@ int vmap_grow(sdm_ctx* c, long long need)
         VmapTable nw{};
         if ((rc = vmap_make_table(c, cap, block, &nw))) return rc;
         HIP_TRY(hipMemsetAsync(v.d_scratch, 0, 8, c->stream));  // (the counters: the caller has sized the scratch)
-        launch_sliced((long long)((v.cap + BLOCK - 1) / BLOCK), [&](long long b0, unsigned g) {
+        launch_sliced(c, (long long)((v.cap + BLOCK - 1) / BLOCK), [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vmap_rehash, dim3(g), dim3(BLOCK), 0, c->stream, v.tb.keys, v.tb.id, v.cap,
                                (unsigned long long)b0 * BLOCK, nw, reinterpret_cast<unsigned*>(v.d_scratch));
         });
@@ -388,7 +388,7 @@ int vmap_count_and_total(sdm_ctx* c, const VmapRecords& rec, const VmapScratch& 
 {
     sdm_ctx::Vmap& v = c->vmap;
     const Scan &nw = s.scan.s[0], &upd = s.scan.s[1];
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vmap_count, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, rec, s.where, items, t0, nw.cnt, upd.cnt);
     });
     scan_counts(c, nw, s.tiles);
@@ -405,7 +405,7 @@ int vmap_count_and_total(sdm_ctx* c, const VmapRecords& rec, const VmapScratch& 
 // the entries of s.where that k_vmap_count found new get their ids, from `first` on in order of first appearance
 void vmap_assign_ids(sdm_ctx* c, const VmapRecords& rec, const VmapScratch& s, unsigned first, long long items)
 {
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vmap_ids, dim3(g), dim3(BLOCK), 0, c->stream, c->vmap.tb, rec, s.where, first, items, t0,
                            s.scan.s[0].off, s.scan.s[0].boff);
     });
@@ -416,7 +416,7 @@ void vmap_assign_ids(sdm_ctx* c, const VmapRecords& rec, const VmapScratch& s, u
 void vobs_count(sdm_ctx* c, const VobsScratch& s, long long items)
 {
     sdm_ctx::Vmap::Obs& o = c->vmap.obs;
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vobs_count, dim3(g), dim3(BLOCK), 0, c->stream, o.tb, s.where, items, t0, s.scan.cnt);
     });
     scan_counts(c, s.scan, s.tiles);
@@ -426,7 +426,7 @@ void vobs_count(sdm_ctx* c, const VobsScratch& s, long long items)
 void vobs_commit(sdm_ctx* c, const VobsScratch& s, unsigned first, long long items)
 {
     sdm_ctx::Vmap::Obs& o = c->vmap.obs;
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vobs_commit, dim3(g), dim3(BLOCK), 0, c->stream, o.tb, o.log, o.last_obs, o.ncam, s.where, first, items,
                            t0, s.scan.off, s.scan.boff);
     });
@@ -443,7 +443,7 @@ int vobs_rebuild_through_remap(sdm_ctx* c, const unsigned* d_remap, long long M,
     HIP_TRY(vobs_reset_table(c, o.tb));
     HIP_TRY(vobs_reset_entries(c, o.last_obs, o.ncam));
     HIP_TRY(hipMemsetAsync(s.head.mid, 0, 24, c->stream));
-    launch_sliced((E + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (E + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vobs_import_insert, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned*)o.log.entry,
                            (const int*)o.log.tag, d_remap, M, E, b0 * BLOCK, (unsigned)M2, o.tb, s.where, s.head.mid, d_pmark);
     });
@@ -645,7 +645,7 @@ int sdm_vmap_integrate(sdm_ctx* c, int n, const int* slots, const int* tags, int
 
     HIP_TRY(hipMemsetAsync(s.head.ctr, 0, 8, c->stream));
     HIP_TRY(hipMemcpyAsync(d_tags, h_tags, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    launch_sliced((T + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (T + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vmap_insert, dim3(g), dim3(BLOCK), 0, c->stream, st.at.xyz, st.at.rho_sigma, T, b0 * BLOCK, v.inv, v.tb,
                            s.where, s.head.ctr);
     });
@@ -655,7 +655,7 @@ int sdm_vmap_integrate(sdm_ctx* c, int n, const int* slots, const int* tags, int
     unsigned* d_upd = !upd_dst ? nullptr : stage_upd ? reinterpret_cast<unsigned*>(v.d_out) : upd_dst;
     const unsigned first_created = (unsigned)v.M, epoch = (unsigned)(v.calls + 1);
     vmap_assign_ids(c, v.rec, s, first_created, T);
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vmap_commit, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, v.rec, s.where, first_created, epoch, T, t0,
                            s.scan.s[1].off, s.scan.s[1].boff, st.at, st.d_offsets, d_tags, n, d_upd);
     });
@@ -713,7 +713,7 @@ int sdm_vmap_fetch(sdm_ctx* c, const unsigned* ids, long long first, long long c
                  if (epoch) dst.epoch = k.take<unsigned>(m);
              }, &f)))
             return rc;
-        launch_sliced((count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+        launch_sliced(c, (count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vmap_gather, dim3(g), dim3(BLOCK), 0, c->stream, v.rec, f.d_ids, count, b0 * BLOCK, (unsigned)v.M, dst,
                                f.d_bad);
         });
@@ -843,7 +843,7 @@ int sdm_vmap_carve(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nb
     in.end_margin = cv->end_margin;
     in.max_steps = cv->max_steps;
     const long long E = ((long long)D + 1) * T;  // candidates, camera-major
-    launch_sliced((E + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (E + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vmap_carve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, E, v.tb, v.crossings, v.ends, d_tot);
     });
     HIP_TRY(hipGetLastError());
@@ -884,7 +884,7 @@ int sdm_vmap_fetch_evidence(sdm_ctx* c, const unsigned* ids, long long first, lo
                  dst_cr = ev->crossings ? cr : nullptr, dst_en = ev->ends ? en : nullptr;
              }, &f)))
             return rc;
-        launch_sliced((count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+        launch_sliced(c, (count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vmap_evidence, dim3(g), dim3(BLOCK), 0, c->stream, src_cr, src_en, f.d_ids, count, b0 * BLOCK,
                                (unsigned)v.M, dst_cr, dst_en, f.d_bad);
         });
@@ -930,7 +930,7 @@ static int vobs_grow(sdm_ctx* c, long long need)
             unsigned* h_flag = reinterpret_cast<unsigned*>(o.h_pin);
             hipError_t e = hipMemsetAsync(d_flag, 0, 4, c->stream);
             if (e == hipSuccess) {
-                launch_sliced((long long)((o.cap + BLOCK - 1) / BLOCK), [&](long long b0, unsigned g) {
+                launch_sliced(c, (long long)((o.cap + BLOCK - 1) / BLOCK), [&](long long b0, unsigned g) {
                     hipLaunchKernelGGL(k_vobs_rehash, dim3(g), dim3(BLOCK), 0, c->stream, o.tb.keys, o.tb.idx, o.cap,
                                        (unsigned long long)b0 * BLOCK, nw, d_flag);
                 });
@@ -1076,7 +1076,7 @@ int sdm_vmap_observe(sdm_ctx* c, int n, const int* slots, const int* tags, int n
     in.n = n;
     in.Lmax = Lmax;
     in.inv = v.inv;
-    launch_sliced((Ec + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (Ec + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vobs_insert, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, Ec, v.tb, o.tb, s.where, s.head.mid);
     });
     vobs_count(c, s, Ec);
@@ -1181,7 +1181,7 @@ int sdm_vmap_fetch_cameras(sdm_ctx* c, const unsigned* ids, long long first, lon
     }
     HIP_TRY(hipMemsetAsync(o.d_scratch, 0, 16, c->stream));
     const long long blocks = (count + BLOCK - 1) / BLOCK, oblocks = (count + 1 + BLOCK - 1) / BLOCK;
-    launch_sliced(blocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, blocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vobs_list_count, dim3(g), dim3(BLOCK), 0, c->stream, o.ncam, d_ids, first, count, b0 * BLOCK,
                            (unsigned)v.M, len.cnt, d_bad);
     });
@@ -1205,12 +1205,12 @@ int sdm_vmap_fetch_cameras(sdm_ctx* c, const unsigned* ids, long long first, lon
         d_tags = reinterpret_cast<int*>(o.d_out);
     }
     if (d_offs)
-        launch_sliced(oblocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, oblocks, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vobs_list_offsets, dim3(g), dim3(BLOCK), 0, c->stream, len.off, len.boff, count, b0 * BLOCK, d_offs,
                                d_total);
         });
     if (cams->cam_tags && total)
-        launch_sliced(blocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, blocks, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vobs_list_fill, dim3(g), dim3(BLOCK), 0, c->stream, o.log, o.last_obs, d_ids, first, count,
                                b0 * BLOCK, (unsigned)v.M, len.cnt, len.off, len.boff, d_tags);
         });
@@ -1285,10 +1285,10 @@ int sdm_vmap_classify(sdm_ctx* c, const sdm_vmap_rule* rule, int commit, sdm_vma
     in.ncam = v.obs.ncam;
     in.crossings = v.crossings;
     in.ends = v.ends;
-    launch_sliced((M + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (M + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vcls_local, dim3(g), dim3(BLOCK), 0, c->stream, in, r, M, b0 * BLOCK, d_flag);
     });
-    launch_sliced(vt, [&](long long t0, unsigned g) {
+    launch_sliced(c, vt, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vcls_count, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, v.rec.xyz, v.inv, r.min_neighbours, M, t0, d_flag,
                            v.cls.d_pub, acc.cnt, ret.cnt);
     });
@@ -1318,7 +1318,7 @@ int sdm_vmap_classify(sdm_ctx* c, const sdm_vmap_rule* rule, int commit, sdm_vma
             if (list_acc) d_acc = reinterpret_cast<unsigned*>(v.d_out);
             if (list_ret) d_ret = reinterpret_cast<unsigned*>(v.d_out + acc_b);
         }
-        launch_sliced(vt, [&](long long t0, unsigned g) {
+        launch_sliced(c, vt, [&](long long t0, unsigned g) {
             hipLaunchKernelGGL(k_vcls_commit, dim3(g), dim3(BLOCK), 0, c->stream, d_flag, v.cls.d_pub, commit, M, t0, acc.off, acc.boff,
                                ret.off, ret.boff, d_acc, d_ret);
         });
@@ -1369,7 +1369,7 @@ int sdm_vmap_fetch_published(sdm_ctx* c, const unsigned* ids, long long first, l
     } else {
         unsigned char* dst = out->published;
         if ((rc = fetch_stage_ids(c, ids, m, dev, [&](Carver& k) { dst = k.take<unsigned char>(m); }, &f))) return rc;
-        launch_sliced((count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+        launch_sliced(c, (count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vcls_gather, dim3(g), dim3(BLOCK), 0, c->stream, src, f.d_ids, count, b0 * BLOCK, (unsigned)v.M, dst,
                                f.d_bad);
         });
@@ -1455,7 +1455,7 @@ int sdm_vmap_import(sdm_ctx* c, const sdm_point_buffers* src, const sdm_vmap_fie
     HIP_TRY(hipMemsetAsync(s.head.ctr, 0, 8, c->stream));
     HIP_TRY(hipMemsetAsync(s.head.tot + 4, 0, 8, c->stream));
     const long long pblocks = (R + BLOCK - 1) / BLOCK;
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vimp_insert, dim3(g), dim3(BLOCK), 0, c->stream, in, R, b0 * BLOCK, v.inv, v.tb, s.where, s.head.ctr,
                            s.head.tot + 4);
     });
@@ -1467,11 +1467,11 @@ int sdm_vmap_import(sdm_ctx* c, const sdm_point_buffers* src, const sdm_vmap_fie
     unsigned* d_upd = !upd_dst ? nullptr : stage_out ? reinterpret_cast<unsigned*>(v.d_out + ids_b) : upd_dst;
     const unsigned first_created = (unsigned)v.M, epoch = (unsigned)(v.calls + 1);
     vmap_assign_ids(c, v.rec, s, first_created, R);
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vimp_commit, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, v.rec, s.where, first_created, R, t0,
                            s.scan.s[1].off, s.scan.s[1].boff, d_upd);
     });
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vimp_write, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, v.rec, s.where, first_created, epoch, R, b0 * BLOCK,
                            in, d_ids, (const unsigned*)nullptr);
     });
@@ -1546,7 +1546,7 @@ int sdm_vmap_import_observations(sdm_ctx* c, long long count, sdm_vmap_obs_impor
         if (mm) HIP_TRY(stage_in(c, d_map, io->entry_map, 4 * mm));
     }
     HIP_TRY(hipMemsetAsync(s.head.mid, 0, 24, c->stream));
-    launch_sliced((P + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (P + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vobs_import_insert, dim3(g), dim3(BLOCK), 0, c->stream, d_entry, d_tag, d_map, io->map_count, P,
                            b0 * BLOCK, (unsigned)v.M, o.tb, s.where, s.head.mid, (const unsigned char*)nullptr);
     });
@@ -1668,7 +1668,7 @@ int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, co
     HIP_TRY(hipMemsetAsync(s.head.base, 0, 512, c->stream));
     if (np) HIP_TRY(hipMemcpyAsync(d_tags, h_tags, tags_b + poses_b, hipMemcpyHostToDevice, c->stream));
     const long long pblocks = (M + BLOCK - 1) / BLOCK;
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vrep_project, dim3(g), dim3(BLOCK), 0, c->stream, v.rec, M, b0 * BLOCK, d_tags, d_poses, n_poses, d_xyz,
                            d_rep);
     });
@@ -1677,7 +1677,7 @@ int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, co
     VimpSrc in{};
     in.xyz = d_xyz, in.rho_sigma = v.rec.rho_sigma, in.pixel = v.rec.pixel;
     in.intensity = v.rec.intensity, in.tag = v.rec.tag, in.multiplicity = v.rec.multiplicity;
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vimp_insert, dim3(g), dim3(BLOCK), 0, c->stream, in, M, b0 * BLOCK, v.inv, v.tb, s.where, s.head.ctr,
                            s.head.tot + 4);
     });
@@ -1685,23 +1685,23 @@ int sdm_vmap_repose(sdm_ctx* c, int n_poses, const int* tags, const float* K, co
     const long long M2 = (long long)h_tot[0], dropped = (long long)h_tot[2];
 
     vmap_assign_ids(c, nw.r, s, 0u, M);
-    launch_sliced(s.tiles, [&](long long t0, unsigned g) {
+    launch_sliced(c, s.tiles, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vimp_commit, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, nw.r, s.where, 0u, M, t0, s.scan.s[1].off,
                            s.scan.s[1].boff, (unsigned*)nullptr);
     });
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vimp_write, dim3(g), dim3(BLOCK), 0, c->stream, v.tb, nw.r, s.where, 0u, 0u, M, b0 * BLOCK, in, d_remap,
                            (const unsigned*)v.rec.epoch);
     });
     // counters and flags: carried through remap into the second set, or back to 0 where they are
     if (carry && (nw.evid.p || nw.pub.p)) {
-        launch_sliced(pblocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vrep_carry, dim3(g), dim3(BLOCK), 0, c->stream, d_remap, M, b0 * BLOCK,
                                nw.evid.p ? v.crossings : nullptr, nw.evid.p ? v.ends : nullptr, nw.crossings, nw.ends,
                                nw.pub.p ? v.cls.d_pub : nullptr, nw.pub.p);
         });
         if (nw.pub.p)
-            launch_sliced((M2 + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+            launch_sliced(c, (M2 + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
                 hipLaunchKernelGGL(k_vrep_count, dim3(g), dim3(BLOCK), 0, c->stream, nw.pub.p, M2, b0 * BLOCK, d_rep + 2);
             });
     } else if (!carry) {
@@ -1833,27 +1833,27 @@ int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vma
     if (nt) HIP_TRY(hipMemcpyAsync(d_tags, h_tags, 4 * nt, hipMemcpyHostToDevice, c->stream));
     if (unobserved) HIP_TRY(hipMemsetAsync(d_seen, 0, m, c->stream));
     const long long pblocks = (M + BLOCK - 1) / BLOCK, eblocks = (E + BLOCK - 1) / BLOCK;
-    launch_sliced(eblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, eblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vret_pairs, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned*)o.log.entry, (const int*)o.log.tag, E,
                            b0 * BLOCK, (unsigned)M, (const int*)d_tags, n_tags, d_pmark, unobserved ? d_seen : (unsigned char*)nullptr);
     });
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vret_entries, dim3(g), dim3(BLOCK), 0, c->stream, (const int*)v.rec.tag, (const unsigned char*)v.cls.d_pub,
                            unobserved ? (const unsigned char*)d_seen : (const unsigned char*)nullptr, M, b0 * BLOCK,
                            (const int*)d_tags, n_tags, d_emark, head.mid);
     });
-    launch_sliced(vt, [&](long long t0, unsigned g) {
+    launch_sliced(c, vt, [&](long long t0, unsigned g) {
         hipLaunchKernelGGL(k_vret_count, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned char*)d_emark, 1u, 1u, 0u, M, t0,
                            stay.cnt, drop.cnt);
     });
     scan_counts(c, stay, vt);
     scan_counts(c, drop, vt);
     if (E > 0) {
-        launch_sliced(eblocks, [&](long long b0, unsigned g) {
+        launch_sliced(c, eblocks, [&](long long b0, unsigned g) {
             hipLaunchKernelGGL(k_vret_vanish, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned*)o.log.entry, E, b0 * BLOCK,
                                (unsigned)M, (const unsigned char*)d_emark, d_pmark);
         });
-        launch_sliced(ot, [&](long long t0, unsigned g) {
+        launch_sliced(c, ot, [&](long long t0, unsigned g) {
             hipLaunchKernelGGL(k_vret_count, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned char*)d_pmark, 3u,
                                (unsigned)VRET_REMOVED, (unsigned)VRET_VANISHED, E, t0, rem.cnt, van.cnt);
         });
@@ -1899,12 +1899,12 @@ int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vma
         if (list_rem && rtag_dst) d_rtag = reinterpret_cast<int*>(v.d_out + drop_b + dpub_b + rem_b);
     }
     if (commit || remap_dst || list_drop)
-        launch_sliced(vt, [&](long long t0, unsigned g) {
+        launch_sliced(c, vt, [&](long long t0, unsigned g) {
             hipLaunchKernelGGL(k_vret_remap, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned char*)d_emark, M, t0, stay.off,
                                stay.boff, drop.off, drop.boff, commit || remap_dst ? d_remap : (unsigned*)nullptr, d_drop, d_dpub);
         });
     if (list_rem)
-        launch_sliced(ot, [&](long long t0, unsigned g) {
+        launch_sliced(c, ot, [&](long long t0, unsigned g) {
             hipLaunchKernelGGL(k_vret_removed, dim3(g), dim3(BLOCK), 0, c->stream, (const unsigned char*)d_pmark,
                                (const unsigned*)o.log.entry, (const int*)o.log.tag, E, t0, rem.off, rem.boff, d_rem, d_rtag);
         });
@@ -1922,7 +1922,7 @@ int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vma
     }
 
     // records (with carry: counters and flags) into the second set; the table emptied and filled from the new records
-    launch_sliced(pblocks, [&](long long b0, unsigned g) {
+    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vret_records, dim3(g), dim3(BLOCK), 0, c->stream, v.rec, nw.r, (const unsigned*)d_remap, M, b0 * BLOCK,
                            nw.evid.p ? (const unsigned long long*)v.crossings : nullptr,
                            nw.evid.p ? (const unsigned long long*)v.ends : nullptr, nw.crossings, nw.ends,
@@ -1933,7 +1933,7 @@ int sdm_vmap_retire(sdm_ctx* c, int n_tags, const int* tags, int commit, sdm_vma
         if (v.cls.d_pub) HIP_TRY(vmap_zero_published(c, v.cls.d_pub, v.rec_cap));
     }
     HIP_TRY(vmap_reset_table(c, v.tb));
-    launch_sliced((M2 + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (M2 + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vret_table, dim3(g), dim3(BLOCK), 0, c->stream, (const float*)nw.r.xyz, M2, b0 * BLOCK, v.inv, v.tb,
                            head.ctr);
     });
@@ -2019,7 +2019,7 @@ int sdm_vmap_recarve(sdm_ctx* c, int n_poses, const int* tags, const float* Tcw,
     in.inv = v.inv;
     in.end_margin = rc->end_margin;
     in.max_steps = rc->max_steps;
-    launch_sliced((count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
+    launch_sliced(c, (count + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
         hipLaunchKernelGGL(k_vmap_recarve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, v.tb, v.crossings, v.ends, head.tot);
     });
     HIP_TRY(hipGetLastError());
