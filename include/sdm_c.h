@@ -1145,6 +1145,79 @@ typedef struct {
 } sdm_vmap_recarve_args;
 int sdm_vmap_recarve(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses], host*/,
                      const float *Tcw /*[n_poses][12], host*/, sdm_vmap_recarve_args *rc);
+/* Ray queries on the voxel map: every call above writes the map or lists its entries by id; these two ask it the spatial
+ * question -- along this segment, which entry comes first?  sdm_vmap_cast_segments answers it for n caller-given segments,
+ * sdm_vmap_render for one segment per pixel of a camera (K, Tcw) that lives in no slot: the view the map predicts for that
+ * pose, the occlusion test of an (entry, camera) pair, the entry under a pixel.  The semantics are this library's
+ * (tests/vmap_cast_np.py restates them).  Both require an open map and only read it.
+ *   - Segment and walk: a ray is a segment from O to P, both float[3].  The cells cO, cP, the skip rule, N = sum_a |cP_a -
+ *     cO_a|, step, r, tMax, tDel, the axis choice with its tie rule and the update are
+ *     sdm_extract_points_voxel_freespace's, word for word, with the map's voxel_size and inv; IEEE binary32, no FMA, the
+ *     plain division.  A ray is SKIPPED if any of the six cells is outside [-2^20, 2^20) (every compare is false for a NaN)
+ *     or if N > max_steps.  cur at index s is the ray's cell of index s, for s = 0 .. N: s = 0 is O's cell, s = N is P's.
+ *   - Examined cells: start_margin <= s <= N - end_margin, in increasing s (none if start_margin > N - end_margin).
+ *     end_margin = 0 examines the end cell.  sdm_vmap_carve's and sdm_vmap_recarve's end_margin = m counts the same cells
+ *     as end_margin = m + 1 here.
+ *   - Filter: an examined cell STOPS the ray iff its key has an entry id with multiplicity[id] >= min_multiplicity and,
+ *     when require_published != 0, published[id] != 0 (if no classify has run every flag reads 0).  An entry that fails
+ *     the filter is transparent: the ray goes on.
+ *   - Per ray: the first stopping cell gives hit_id = its id and hit_step = its s; a walked ray without one gives hit_id =
+ *     SDM_VMAP_NO_HIT and hit_step = 0; a skipped ray hit_id = SDM_VMAP_RAY_SKIPPED and hit_step = 0.  Ids stay below
+ *     2^30, so the two codes collide with none.
+ *   - Totals: rays_total; rays_skipped; rays_hit; cells_visited = the examined cells up to and including the stopping one,
+ *     summed over the walked rays.
+ * sdm_vmap_cast_segments: ray i is (origins[i], ends[i]).  origins, ends, hit_id and hit_step all follow args->on_device
+ * (there: 4-byte aligned); hit_id and hit_step hold args->capacity >= n elements and either may be NULL, not both.  hit_rho
+ * is ignored.  n == 0 is valid.
+ * sdm_vmap_render: one ray per pixel, ray i = y * W + x from O to P(x, y).  K[4] = (fx, fy, cx, cy) and Tcw[12] are host
+ * arrays.  O is the camera centre of Tcw, formed on the host exactly as sdm_vmap_recarve forms it; P(x, y) is the
+ * back-projection of the pixel at inverse depth rho_far by the device function of the point-set pass -- what
+ * sdm_vmap_repose gives an entry with that pixel, that rho and that pose.  hit_id, hit_step and hit_rho follow
+ * args->on_device and hold args->capacity >= W * H elements; any may be NULL, not all three.  For a hit on entry id with
+ * record xyz (X, Y, Z): z = ((Tcw[8]*X + Tcw[9]*Y) + Tcw[10]*Z) + Tcw[11] and hit_rho = 1.0f / z (no FMA, the plain
+ * division); otherwise hit_rho = +0.0f.  The answer is voxel-level: the hit entry's stored point need not project into
+ * that pixel, and hit_rho belongs to the stored point, not to the ray's crossing of the voxel (it is negative or infinite
+ * if that point is not in front of the camera).  A non-finite pose is no error: its rays are skipped.
+ *   - State: neither call changes the map, the log, the counters, the flags, any info struct, or any plane or list of the
+ *     engine.  Everything returned is a pure function of the arguments, the records' cells and multiplicities (render:
+ *     and xyz), and the flags: bitwise the same from run to run, whatever the table layout.
+ * Errors, all raised on the host before anything is queued; the four outs are then 0:
+ *   SDM_EINVAL: a NULL ctx or args.
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: n < 0 or n > 2^30 (render: W or H outside 1 .. 65535, or W * H > 2^30); NULL origins or ends with n > 0
+ *     (render: NULL K or Tcw); no destination at all; capacity < n (render: < W * H); a misaligned device pointer;
+ *     start_margin < 0 or end_margin < 0; max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS; require_published not 0 or 1;
+ *     render: rho_far NaN or (double)rho_far < 1e-6 (the back-projection would return the origin).
+ *   SDM_EHIP: an allocation failure, raised before any launch.
+ * Cost: one lane per ray, ray i on lane i (render: raster order).  Per ray 24 B of segment (render: none), six float
+ * divisions, and per examined cell one read-only probe of the table as in sdm_vmap_carve, plus 4 B of multiplicity (and 1 B
+ * of flag) per entry met; the loop leaves at the first stopping cell.  4 B per ray and requested output are written.  Host
+ * sources and destinations pass through engine staging (24 B / 4 B per ray and field): one copy per field of exactly n
+ * elements.  One host wait: the end, with 32 B of totals.  Measured: DESIGN.md s.26.
+ * Limits: one rank only; the answer is per voxel, at the winning point -- no sub-voxel intersection, no normals; positions
+ * go stale with sdm_set_pose exactly as the records do (sdm_vmap_repose re-places them). */
+#define SDM_VMAP_NO_HIT 0xFFFFFFFFu
+#define SDM_VMAP_RAY_SKIPPED 0xFFFFFFFEu
+typedef struct {
+    int start_margin;          /* in: >= 0; the first start_margin cells of the ray are not examined */
+    int end_margin;            /* in: >= 0; the last end_margin cells are not examined (0: the end cell is) */
+    int max_steps;             /* in: 1 .. SDM_FREESPACE_MAX_STEPS; a longer ray is skipped, not truncated */
+    unsigned min_multiplicity; /* in: entries with fewer points are transparent */
+    int require_published;     /* in: 0 or 1; 1: unpublished entries are transparent */
+    int on_device;             /* in: the arrays below (and origins / ends) are device pointers */
+    long long capacity;        /* in: elements each destination holds */
+    unsigned *hit_id;          /* [capacity] or NULL */
+    int *hit_step;             /* [capacity] or NULL */
+    float *hit_rho;            /* [capacity] or NULL; sdm_vmap_render only */
+    long long rays_total;      /* out */
+    long long rays_skipped;    /* out */
+    long long rays_hit;        /* out */
+    long long cells_visited;   /* out */
+} sdm_vmap_cast_args;
+int sdm_vmap_cast_segments(sdm_ctx *ctx, long long n, const float *origins /*[n][3]*/, const float *ends /*[n][3]*/,
+                           sdm_vmap_cast_args *args);
+int sdm_vmap_render(sdm_ctx *ctx, const float *K /*[4], host*/, const float *Tcw /*[12], host*/, int W, int H, float rho_far,
+                    sdm_vmap_cast_args *args);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

@@ -176,6 +176,14 @@ class VmapRecarveArgs(C.Structure):
                 ("cells_hit", C.c_longlong), ("ends_hit", C.c_longlong)]
 
 
+class VmapCastArgs(C.Structure):
+    """sdm_vmap_cast_args"""
+    _fields_ = [("start_margin", C.c_int), ("end_margin", C.c_int), ("max_steps", C.c_int), ("min_multiplicity", C.c_uint),
+                ("require_published", C.c_int), ("on_device", C.c_int), ("capacity", C.c_longlong), ("hit_id", C.c_void_p),
+                ("hit_step", C.c_void_p), ("hit_rho", C.c_void_p), ("rays_total", C.c_longlong),
+                ("rays_skipped", C.c_longlong), ("rays_hit", C.c_longlong), ("cells_visited", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -217,6 +225,10 @@ VMAP_RETIRE_LISTS = {"remap": (np.uint32, "remap_capacity", "examined"),
                      "removed_tag": (np.int32, "removed_capacity", "removed")}
 # the outs of sdm_vmap_recarve
 VMAP_RECARVE_OUTS = ("pairs_total", "pairs_unposed", "rays_total", "rays_skipped", "cells_visited", "cells_hit", "ends_hit")
+# sdm_vmap_cast_segments / sdm_vmap_render: the two codes of hit_id, the outs, and the destinations with their dtypes
+VMAP_NO_HIT, VMAP_RAY_SKIPPED = 0xFFFFFFFF, 0xFFFFFFFE
+VMAP_CAST_OUTS = ("rays_total", "rays_skipped", "rays_hit", "cells_visited")
+VMAP_CAST_FIELDS = {"hit_id": np.uint32, "hit_step": np.int32, "hit_rho": np.float32}
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -298,6 +310,8 @@ SYMBOLS = [
     ("sdm_vmap_repose", C.c_int, [_ctx, C.c_int, _ip, _f32p, _f32p, C.POINTER(VmapReposeDelta)]),
     ("sdm_vmap_retire", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.POINTER(VmapRetireDelta)]),
     ("sdm_vmap_recarve", C.c_int, [_ctx, C.c_int, _ip, _f32p, C.POINTER(VmapRecarveArgs)]),
+    ("sdm_vmap_cast_segments", C.c_int, [_ctx, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(VmapCastArgs)]),
+    ("sdm_vmap_render", C.c_int, [_ctx, _f32p, _f32p, C.c_int, C.c_int, C.c_float, C.POINTER(VmapCastArgs)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1604,6 +1618,78 @@ class Engine:
         rc.first, rc.count = int(first), -1 if count is None else int(count)
         self._check(self.lib.sdm_vmap_recarve(self.ctx, n, tp, pp, C.byref(rc)))
         return {f: int(getattr(rc, f)) for f in VMAP_RECARVE_OUTS}
+
+    def _cast_args(self, n, kinds, like, wanted, start_margin, end_margin, max_steps, min_multiplicity, require_published):
+        """(sdm_vmap_cast_args, {field: destination}) for n rays.  wanted: {field: True -- made here, where the sources are
+        (device: int32 / float32 tensors holding the same bits); False / None -- not returned; or the destination}"""
+        a = VmapCastArgs()
+        a.start_margin, a.end_margin, a.max_steps = int(start_margin), int(end_margin), int(max_steps)
+        a.min_multiplicity, a.require_published = int(min_multiplicity), int(require_published)
+        dest, cap = {}, None
+        for f, w in wanted.items():
+            if w is None or w is False:
+                continue
+            if w is True:
+                if kinds == {"device"}:
+                    import torch  # (a device tensor was passed in: torch is loaded)
+                    w = like.new_empty(max(n, 1), dtype=torch.float32 if f == "hit_rho" else torch.int32)
+                else:
+                    w = np.empty(max(n, 1), VMAP_CAST_FIELDS[f])
+            ptr, m = self._dest(f, w, VMAP_CAST_FIELDS[f], 1, kinds)
+            if like is None and not isinstance(w, np.ndarray):
+                like = w
+            setattr(a, f, ptr)
+            cap = m if cap is None else min(cap, m)
+            dest[f] = w
+        if len(kinds) > 1:
+            raise ValueError("sources and destinations mix host arrays and device tensors")
+        a.capacity = 0 if cap is None else cap
+        a.on_device = 1 if kinds == {"device"} else 0
+        return a, dest
+
+    def vmap_cast_segments(self, origins, ends, start_margin=0, end_margin=0, max_steps=4096, min_multiplicity=0,
+                           require_published=False, steps=True, ids=True):
+        """First hit along segments through the voxel map (sdm_vmap_cast_segments).  origins and ends float32[n, 3]: NumPy
+        arrays, or torch tensors on this engine's GPU (both of one kind).  Ray i runs from origins[i] to ends[i] through
+        the map's voxels; its cells start_margin .. N - end_margin are examined and the first whose entry has at least
+        min_multiplicity points (and, with require_published, is published) stops it.  Returns {"hit_id" uint32[n] (the
+        entry, VMAP_NO_HIT, or VMAP_RAY_SKIPPED), "hit_step" int32[n], "rays_total", "rays_skipped", "rays_hit",
+        "cells_visited"}.  ids / steps: True -- made here, where the rays are (device: int32 tensors holding the same
+        bits); False -- not returned; or the destination.  The map is only read."""
+        kinds = set()
+        src = []
+        for f, s in (("origins", origins), ("ends", ends)):
+            if isinstance(s, np.ndarray) or not getattr(s, "is_cuda", False):
+                s = np.ascontiguousarray(np.asarray(s, dtype=np.float32).reshape(-1, 3))
+            src.append((s,) + self._dest(f, s, np.float32, 3, kinds))
+        n = src[0][2]
+        if src[1][2] != n:
+            raise ValueError("origins and ends: need the same length")
+        a, dest = self._cast_args(n, kinds, src[0][0], {"hit_id": ids, "hit_step": steps}, start_margin, end_margin, max_steps,
+                                  min_multiplicity, require_published)
+        self._check(self.lib.sdm_vmap_cast_segments(self.ctx, n, src[0][1] if n else None, src[1][1] if n else None, C.byref(a)))
+        res = {f: d[:n] for f, d in dest.items()}
+        res.update({f: int(getattr(a, f)) for f in VMAP_CAST_OUTS})
+        return res
+
+    def vmap_render(self, K, Tcw, W, H, rho_far, start_margin=0, end_margin=0, max_steps=4096, min_multiplicity=0,
+                    require_published=False, ids=True, steps=True, rho=True):
+        """What the voxel map predicts for a camera (sdm_vmap_render): one ray per pixel of a W x H image under K = (fx, fy,
+        cx, cy) and Tcw float32[12], from the camera centre to the pixel's back-projection at inverse depth rho_far,
+        answered as vmap_cast_segments answers a segment.  Returns {"hit_id" uint32[H, W], "hit_step" int32[H, W], "hit_rho"
+        float32[H, W]: 1 / z of the hit entry's stored point in the camera, +0 where nothing was hit, "rays_total",
+        "rays_skipped", "rays_hit", "cells_visited"}.  ids / steps / rho: True -- a NumPy array is made here; False -- not
+        returned; or the destination, an array (pageable, or pinned from host_alloc) or a torch device tensor of 4-byte
+        elements with at least W * H of them (all of one kind).  The map is only read."""
+        k4, kp = _f32(np.asarray(K, dtype=np.float32).reshape(4))
+        t12, pp = _f32(np.asarray(Tcw, dtype=np.float32).reshape(12))
+        n = int(W) * int(H)
+        a, dest = self._cast_args(n, set(), None, {"hit_id": ids, "hit_step": steps, "hit_rho": rho}, start_margin, end_margin,
+                                  max_steps, min_multiplicity, require_published)
+        self._check(self.lib.sdm_vmap_render(self.ctx, kp, pp, int(W), int(H), float(rho_far), C.byref(a)))
+        res = {f: d.reshape(-1)[:n].reshape(int(H), int(W)) for f, d in dest.items()}
+        res.update({f: int(getattr(a, f)) for f in VMAP_CAST_OUTS})
+        return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
         """the most points extract_points can return for these arguments (sdm_extract_bound)"""
