@@ -1218,6 +1218,67 @@ int sdm_vmap_cast_segments(sdm_ctx *ctx, long long n, const float *origins /*[n]
                            sdm_vmap_cast_args *args);
 int sdm_vmap_render(sdm_ctx *ctx, const float *K /*[4], host*/, const float *Tcw /*[12], host*/, int W, int H, float rho_far,
                     sdm_vmap_cast_args *args);
+/* Connected components of the voxel map's entries: every filter above is local -- one entry's counters, the occupancy of its
+ * 26 adjacent cells -- and cannot see a small floating island; this call answers the global question: which entries belong
+ * to a connected piece of at least k voxels, and which do not?  The semantics are this library's (tests/vmap_comp_np.py
+ * restates them).  It requires an open map and only reads it.
+ *   - Members: entry id is a MEMBER iff multiplicity[id] >= min_multiplicity and, when require_published != 0,
+ *     published[id] != 0 (if no classify has run every flag reads 0): the filter of the ray queries above.
+ *   - Cell: the cell of an entry is floorf(xyz_k * inv) of its record, as sdm_vmap_classify forms it.
+ *   - Adjacency: two cells are adjacent iff they differ by an offset d in {-1, 0, 1}^3, d != 0, with |dx| + |dy| + |dz| <=
+ *     1, 2, 3 for connectivity = 6, 18, 26.  A cell with a coordinate outside [-2^20, 2^20) holds nothing: the range test
+ *     comes before the key is formed, so the last cell of one row is never taken for the first cell of the next.
+ *   - Components: the classes of the transitive closure of "both members, cells adjacent".
+ *   - Per entry (arrays of M elements, in id order): label[id] = the smallest id of its component; size[id] = the number
+ *     of members of its component.  A non-member gets label SDM_VMAP_NO_COMPONENT and size 0.  Ids stay below 2^30, so the
+ *     code collides with none.
+ *   - Small list: with min_size > 0, small_ids is the ascending list of the members whose component has fewer than
+ *     min_size members -- the ids a consumer drops, or emits a deletion for.  min_size == 0 lists nothing.
+ *   - Totals: entries = M; members; components = the ids with label[id] == id; largest = the size of the largest
+ *     component (0 without members); small = the length of the small list; small_components = the components it comes from.
+ * label, size and small_ids follow args->on_device (there: 4-byte aligned).  label and size hold args->capacity >= M
+ * elements, small_ids holds args->small_capacity.  Any of them may be NULL; all three NULL is valid and gives the totals
+ * only.  M == 0 is valid and queues nothing.
+ *   - Capacity: small > small_capacity with small_ids != NULL is SDM_EINVAL; the six totals are filled and no destination
+ *     is written (sdm_vmap_classify's contract: counts first, one wait, and the writing launch is queued only if the call
+ *     is not refused).  The caller sizes the array and calls again.
+ *   - State: the call changes no record, id, evidence counter, flag or log entry, no field of any info struct, and no plane
+ *     or list of the engine.  Every output is a pure function of the arguments, the records' cells and multiplicities, and
+ *     the flags: bitwise the same from run to run, whatever the table layout and whatever order the device linked things in.
+ * Errors, all raised on the host before anything is queued; the six totals are then 0:
+ *   SDM_EINVAL: a NULL ctx or args.
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: connectivity not 6, 18 or 26; require_published not 0 or 1; a negative capacity or small_capacity;
+ *     capacity < M with label or size given; a misaligned device pointer.
+ *   SDM_EHIP: an allocation failure, raised before any launch.
+ * Cost: one lane per entry.  A lock-free union-find over the map's own table: per member 12 B of record, 3, 9 or 13
+ * read-only probes (each undirected pair of cells is met once) and per link found a walk of parent[] with path halving and
+ * one compare-and-swap; then one walk and one 32-bit add per member, and two passes in tiles for the counts and the
+ * writes.  Scratch: 8 B per entry.  Host destinations pass through engine staging: one copy per array of exactly M
+ * (small_ids: small) elements.  Two host waits: the totals (40 B), then the end.  Measured: DESIGN.md s.27.
+ * Limits: the pass is O(M) per call and not incremental; it is voxel-level -- the winning point's cell; it goes stale with
+ * sdm_set_pose exactly as the records do (sdm_vmap_repose re-places them); there is no hysteresis; the flags are not
+ * touched -- retracting a speckle is the consumer's business, or a later classify's; one rank only. */
+#define SDM_VMAP_NO_COMPONENT 0xFFFFFFFFu
+typedef struct {
+    int connectivity;          /* in: 6, 18 or 26 */
+    unsigned min_multiplicity; /* in: entries with fewer points are no members */
+    int require_published;     /* in: 0 or 1; 1: unpublished entries are no members */
+    unsigned min_size;         /* in: components of fewer members are small; 0: none is */
+    int on_device;             /* in: the arrays below are device pointers */
+    long long capacity;        /* in: elements label and size hold */
+    long long small_capacity;  /* in: elements small_ids holds */
+    unsigned *label;           /* [capacity] or NULL */
+    unsigned *size;            /* [capacity] or NULL */
+    unsigned *small_ids;       /* [small_capacity] or NULL */
+    long long entries;         /* out: M */
+    long long members;         /* out */
+    long long components;      /* out */
+    long long largest;         /* out */
+    long long small;           /* out */
+    long long small_components;/* out */
+} sdm_vmap_comp_args;
+int sdm_vmap_components(sdm_ctx *ctx, sdm_vmap_comp_args *args);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

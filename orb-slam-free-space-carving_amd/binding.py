@@ -184,6 +184,15 @@ class VmapCastArgs(C.Structure):
                 ("rays_skipped", C.c_longlong), ("rays_hit", C.c_longlong), ("cells_visited", C.c_longlong)]
 
 
+class VmapCompArgs(C.Structure):
+    """sdm_vmap_comp_args"""
+    _fields_ = [("connectivity", C.c_int), ("min_multiplicity", C.c_uint), ("require_published", C.c_int), ("min_size", C.c_uint),
+                ("on_device", C.c_int), ("capacity", C.c_longlong), ("small_capacity", C.c_longlong), ("label", C.c_void_p),
+                ("size", C.c_void_p), ("small_ids", C.c_void_p), ("entries", C.c_longlong), ("members", C.c_longlong),
+                ("components", C.c_longlong), ("largest", C.c_longlong), ("small", C.c_longlong),
+                ("small_components", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -229,6 +238,10 @@ VMAP_RECARVE_OUTS = ("pairs_total", "pairs_unposed", "rays_total", "rays_skipped
 VMAP_NO_HIT, VMAP_RAY_SKIPPED = 0xFFFFFFFF, 0xFFFFFFFE
 VMAP_CAST_OUTS = ("rays_total", "rays_skipped", "rays_hit", "cells_visited")
 VMAP_CAST_FIELDS = {"hit_id": np.uint32, "hit_step": np.int32, "hit_rho": np.float32}
+# sdm_vmap_components: the label of a non-member, the outs, and the destinations (all uint32)
+VMAP_NO_COMPONENT = 0xFFFFFFFF
+VMAP_COMP_OUTS = ("entries", "members", "components", "largest", "small", "small_components")
+VMAP_COMP_FIELDS = ("label", "size", "small_ids")
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -312,6 +325,7 @@ SYMBOLS = [
     ("sdm_vmap_recarve", C.c_int, [_ctx, C.c_int, _ip, _f32p, C.POINTER(VmapRecarveArgs)]),
     ("sdm_vmap_cast_segments", C.c_int, [_ctx, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(VmapCastArgs)]),
     ("sdm_vmap_render", C.c_int, [_ctx, _f32p, _f32p, C.c_int, C.c_int, C.c_float, C.POINTER(VmapCastArgs)]),
+    ("sdm_vmap_components", C.c_int, [_ctx, C.POINTER(VmapCompArgs)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1689,6 +1703,49 @@ class Engine:
         self._check(self.lib.sdm_vmap_render(self.ctx, kp, pp, int(W), int(H), float(rho_far), C.byref(a)))
         res = {f: d.reshape(-1)[:n].reshape(int(H), int(W)) for f, d in dest.items()}
         res.update({f: int(getattr(a, f)) for f in VMAP_CAST_OUTS})
+        return res
+
+    def vmap_components(self, connectivity=26, min_multiplicity=0, require_published=False, min_size=0, labels=True,
+                        sizes=True, small_ids=True):
+        """Connected components of the voxel map's entries (sdm_vmap_components).  An entry is a member if it has at least
+        min_multiplicity points (and, with require_published, is published); members in adjacent cells -- by face (6), face
+        or edge (18), or any of the 26 -- are one component.  Returns {"label" uint32[M]: the smallest id of the entry's
+        component, VMAP_NO_COMPONENT for a non-member; "size" uint32[M]: its members, 0 for a non-member; "small_ids"
+        uint32[small]: ascending, the members of components of fewer than min_size members (none for min_size 0);
+        "entries", "members", "components", "largest", "small", "small_components"}.  labels / sizes / small_ids: True -- a
+        NumPy array is made here (small_ids: of M elements, returned cut to small); False -- not returned; or the destination, a
+        uint32 array (pageable, or pinned from host_alloc) or a torch device tensor of 4-byte elements (all of one kind).  A
+        small_ids destination too short raises SdmError with the six totals as attributes; nothing has been written then.
+        The map is only read."""
+        a = VmapCompArgs()
+        a.connectivity, a.min_multiplicity = int(connectivity), int(min_multiplicity)
+        a.require_published, a.min_size = int(require_published), int(min_size)
+        m = None
+        kinds, dest, caps = set(), {}, {}
+        for f, w in zip(VMAP_COMP_FIELDS, (labels, sizes, small_ids)):
+            if w is None or w is False:
+                continue
+            if w is True:
+                if m is None:
+                    m = self.vmap_info()["voxels"]
+                w = np.empty(max(m, 1), np.uint32)
+            ptr, caps[f] = self._dest(f, w, np.uint32, 1, kinds)
+            setattr(a, f, ptr)
+            dest[f] = w
+        if len(kinds) > 1:
+            raise ValueError("the destinations mix host arrays and device tensors")
+        a.capacity = min([caps[f] for f in ("label", "size") if f in caps], default=0)
+        a.small_capacity = caps.get("small_ids", 0)
+        a.on_device = 1 if kinds == {"device"} else 0
+        rc = self.lib.sdm_vmap_components(self.ctx, C.byref(a))
+        if rc:
+            e = SdmError(rc, self.lib.sdm_last_error().decode())
+            for f in VMAP_COMP_OUTS:
+                setattr(e, f, int(getattr(a, f)))
+            raise e
+        res = {f: int(getattr(a, f)) for f in VMAP_COMP_OUTS}
+        for f, w in dest.items():
+            res[f] = w[:res["small"] if f == "small_ids" else res["entries"]]
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):

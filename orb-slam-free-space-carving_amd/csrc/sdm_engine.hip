@@ -46,6 +46,8 @@
 #include "sdm_vmap_poses.h"
 #include "sdm_vmap_cast.h"
 #include "sdm_vmap_cast_check.h"
+#include "sdm_vmap_comp.h"
+#include "sdm_vmap_comp_check.h"
 
 using namespace sdm;
 
@@ -2875,6 +2877,7 @@ int sdm_extract_points_voxel_freespace(sdm_ctx* c, int n, const int* slots, int 
 // ---- the persistent voxel map: every sdm_vmap_* call and the steps they share ---------------------------------------------
 #include "sdm_vmap_host.h"
 #include "sdm_vmap_cast_host.h"
+#include "sdm_vmap_comp_host.h"
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
 
