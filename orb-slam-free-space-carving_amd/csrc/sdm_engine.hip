@@ -638,7 +638,7 @@ size_t select_set(sdm_ctx* c, int si, int n_ref, size_t np)
 // in slices of reference keyframes: fn(first, count) launches one slice.
 // The limit is the context's (sdm_ctx::max_dispatch, 2^31 unless SDM_MAX_DISPATCH_LOG2 / SDM_MAX_DISPATCH_ITEMS said otherwise
 // when the context was created), so a test runs an engine that slices at 2^8 .. 2^10 work-items beside a default one
-// (tests/test_gpu_slices.py): the slice offsets of every call site below and in sdm_vmap_host.h, and what a call carries
+// (tests/test_gpu_slices.py): the slice offsets of every call site below, in sdm_extract_host.h and in sdm_vmap_host.h, and what a call carries
 // from one slice to the next (open list, grow list, per-call counters, scans, totals), are verified that way at test sizes.
 // NOT verified by that: index width beyond 2^31 work-items (test_gpu_fullsize.py reaches for_ref_slices only) and the
 // 2^30 / 2^40 refusals.  A limit below a launch's workgroup size gives one workgroup (one reference) per dispatch.
@@ -2224,655 +2224,9 @@ int sdm_download_pointset(sdm_ctx* c, int slot, float* xyz)
     return SDM_OK;
 }
 
-// ---- filtered point cloud (sdm_extract_points, sdm_extract.h) ----------------------------------------------------------
-// the largest float <= t (NaN for NaN): for every float v, (double)v > t  <=>  v > ext_float_floor(t)
-static float ext_float_floor(double t)
-{
-    const float inf = std::numeric_limits<float>::infinity();
-    if (t != t) return std::numeric_limits<float>::quiet_NaN();
-    if (t >= (double)std::numeric_limits<float>::max()) return t == (double)inf ? inf : std::numeric_limits<float>::max();
-    if (t < -(double)std::numeric_limits<float>::max()) return -inf;
-    float f = (float)t;
-    if ((double)f > t) f = std::nextafterf(f, -inf);
-    return f;
-}
-
-static size_t ext_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// grow a device / pinned buffer to at least `bytes` (the previous call ended with a stream sync: nothing uses it)
-static int ext_grow_dev(unsigned char** p, size_t* have, size_t bytes)
-{
-    if (*have >= bytes) return SDM_OK;
-    HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc((void**)p, bytes));
-    *have = bytes;
-    return SDM_OK;
-}
-static int ext_grow_host(unsigned char** p, size_t* have, size_t bytes)
-{
-    if (*have >= bytes) return SDM_OK;
-    HIP_TRY(hipHostFree(*p));
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
-    *have = bytes;
-    return SDM_OK;
-}
-
-// The slots' checks and walks, shared by sdm_extract_points and sdm_extract_bound: count[i] = items of slot i -- its list
-// length when the list walk covers every pixel that can pass, W*H otherwise.  Waits for list lengths still in flight.
-static int ext_plan(sdm_ctx* c, int n, const int* slots, int source, double min_rho, std::vector<char>& use_list,
-                    std::vector<int>& count)
-{
-    if (n < 0 || (n > 0 && !slots)) return fail(SDM_EINVAL, "null or negative slot list");
-    if (source != 0 && source != 1) return fail(SDM_EINVAL, "source must be 0 (depth map) or 1 (checked plane)");
-    std::vector<char> seen((size_t)c->cfg.max_keyframes, 0);
-    for (int i = 0; i < n; i++) {
-        const int s = slots[i];
-        if (s < 0 || s >= c->cfg.max_keyframes) return fail(SDM_EINVAL, "slot out of range");
-        if (seen[(size_t)s]) return fail(SDM_EINVAL, "slot listed twice");
-        seen[(size_t)s] = 1;
-    }
-    for (int i = 0; i < n; i++) {
-        if (!c->has_depth[slots[i]]) return fail(SDM_ESTATE, "slot has no depth map");
-        if (source && !c->has_chk[slots[i]]) return fail(SDM_ESTATE, "slot has not been inter-keyframe checked");
-    }
-    // per slot: the list path when the rho plane is zero outside the list now in d_act (the flags sdm_pointset decides by;
-    // a depth map counts only while the list is the one of the current lambdaG, which this call does not rebuild) and a
-    // zero rho cannot pass (min_rho < 0 keeps the zeros off the list: those slots are walked whole)
-    const bool zero_fails = !(0.0 > min_rho);
-    use_list.assign((size_t)n, 0);
-    count.assign((size_t)n, (int)c->P);
-    std::vector<int> list_slots;
-    for (int i = 0; i < n; i++) {
-        const int s = slots[i];
-        const bool has_list = c->act_lambdaG[s] == c->act_lambdaG[s];
-        use_list[i] = zero_fails && (source ? (c->chk_sparse[s] && has_list)
-                                            : (c->recon_lambdaG[s] == c->dprm.lambdaG && c->act_lambdaG[s] == c->dprm.lambdaG));
-        if (use_list[i]) list_slots.push_back(s);
-    }
-    int rc;
-    if (!list_slots.empty() && (rc = sync_counts_for(c, (int)list_slots.size(), list_slots.data(), 0, nullptr))) return rc;
-    for (int i = 0; i < n; i++)
-        if (use_list[i]) count[i] = c->h_act_count[slots[i]];
-    return SDM_OK;
-}
-
-int sdm_extract_bound(sdm_ctx* c, int n, const int* slots, int source, double min_rho, long long* bound)
-{
-    if (!c || !bound) return fail(SDM_EINVAL, "null argument");
-    std::vector<char> use_list;
-    std::vector<int> count;
-    int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
-    if (rc) return rc;
-    long long b = 0;
-    for (int i = 0; i < n; i++) b += count[i];
-    *bound = b;
-    return SDM_OK;
-}
-
-// extract_core's hand-over to sdm_extract_points_voxel: the plain cloud left in the engine's staging, not yet waited for
-struct ExtractStaged {
-    bool pixel, intensity;                 // in: stage these besides xyz and rho_sigma
-    bool support;                          // in: stage the pixel codes and the support words too (k_point_support queued)
-    long long total;                       // out: plain points
-    ExtractOut at;                         // out: where they are (d_ext_stage)
-    const unsigned long long* d_offsets;   // out: the plain offsets[n + 1] on the device (d_ext)
-    const unsigned long long* d_support;   // out (support): the words (d_ext_stage)
-    const long long* d_block0;             // out (support): k_point_support's block0[n + 1] on the device (d_ext)
-    long long blocks;                      // out (support): its workgroups
-};
-
-// sdm_extract_points (support == nullptr) and sdm_extract_points_support: the three extraction passes, then -- for the
-// second -- k_point_support over the compacted pixel codes (sdm_support.h).  With `st` (sdm_extract_points_voxel; `out`
-// names no destination then): the passes write xyz, rho_sigma and the fields st asks for into the staging whatever the
-// total, and the call returns with pass 3 (and, if st asks for the words, k_point_support) queued.
-static int extract_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
-                        double min_rho, sdm_point_buffers* out, unsigned long long* support, long long* offsets,
-                        ExtractStaged* st = nullptr)
-{
-    const bool w_xyz = st || out->xyz, w_pix = st ? st->pixel : out->pixel != nullptr, w_rs = st || out->rho_sigma,
-               w_im = st ? st->intensity : out->intensity != nullptr;
-    const bool w_sup = support || (st && st->support);
-    if (st) st->total = 0;
-    if (out->capacity < 0) return fail(SDM_EINVAL, "negative capacity");
-    if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel) % 4 || (uintptr_t)out->rho_sigma % 8))
-        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel: 4 B; rho_sigma: 8 B)");
-    if (out->on_device && (uintptr_t)support % 8) return fail(SDM_EINVAL, "device buffer not aligned (support: 8 B)");
-    std::vector<char> use_list;
-    std::vector<int> count;
-    int rc = ext_plan(c, n, slots, source, min_rho, use_list, count);
-    if (rc) return rc;
-    if (w_xyz && !c->xyz) return fail(SDM_ESTATE, "context created without with_pointset");
-    if (w_sup) {  // sdm_inter_check's checks of the neighbour table (the slots themselves: ext_plan)
-        if (n_nbr < 1) return fail(SDM_EINVAL, "need at least one neighbour");
-        if (n_nbr > c->cfg.max_neighbours) return fail(SDM_EINVAL, "n_nbr exceeds max_neighbours");
-        for (size_t i = 0; i < (size_t)n * (size_t)n_nbr; i++) {
-            const int s = nbr_slots[i];
-            if (s < 0 || s >= c->cfg.max_keyframes) return fail(SDM_EINVAL, "slot out of range");
-            if (!c->has_depth[s])
-                return fail(SDM_ESTATE, "neighbour slot has no depth map (sdm_recon, sdm_upload_depth, an sdm_exchange_* "
-                                        "call or sdm_mark_depth_present must come first)");
-        }
-    }
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // RefConst / PairConst of the call (the set an sdm_inter_check over the same lists staged serves this call too); the
-    // lists are left as they are: this call changes none
-    if (w_sup && n > 0 && (rc = stage_tables(c, n, slots, n_nbr, nbr_slots, nullptr, nullptr, nullptr, false, false))) return rc;
-
-    const size_t tab_b = ext_align(sizeof(ExtractSlot) * (size_t)std::max(n, 1));
-    const size_t offs_b = ext_align(sizeof(unsigned long long) * (size_t)(n + 1));
-    const size_t cut_b = w_sup ? ext_align(sizeof(long long) * (size_t)(n + 1)) : 0;  // first workgroup per slot (k_point_support's block0)
-    if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, tab_b + offs_b + cut_b))) return rc;
-    ExtractSlot* h_tab = reinterpret_cast<ExtractSlot*>(c->h_ext);
-    unsigned long long* h_offs = reinterpret_cast<unsigned long long*>(c->h_ext + tab_b);
-    long long* h_cut = reinterpret_cast<long long*>(c->h_ext + tab_b + offs_b);
-    long long nt = 0;
-    for (int i = 0; i < n; i++) {
-        ExtractSlot& d = h_tab[i];
-        d.tile0 = nt;
-        d.slot = slots[i];
-        d.list = use_list[i] ? 1 : 0;
-        d.count = count[i];
-        d.pad = 0;
-        nt += (d.count + EXT_TILE - 1) / EXT_TILE;
-    }
-    if (nt == 0) {  // nothing to walk: every slot is empty
-        for (int i = 0; i <= n; i++) offsets[i] = 0;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SDM_OK;
-    }
-    const long long nb = (nt + 1 + EXT_SCAN - 1) / EXT_SCAN;  // scan workgroups over the nt + 1 tile offsets
-    if (nb > std::numeric_limits<int>::max() || nt > std::numeric_limits<int>::max())
-        return fail(SDM_EINVAL, "too many tiles in one call");
-    const size_t cnt_b = ext_align(sizeof(unsigned) * (size_t)nt);
-    const size_t toff_b = ext_align(sizeof(unsigned) * (size_t)(nt + 1));
-    const size_t blk_b = ext_align(sizeof(unsigned long long) * (size_t)nb);
-    if ((rc = ext_grow_dev(&c->d_ext, &c->ext_bytes, tab_b + cnt_b + toff_b + 2 * blk_b + offs_b + cut_b))) return rc;
-    ExtractSlot* d_tab = reinterpret_cast<ExtractSlot*>(c->d_ext);
-    unsigned* d_cnt = reinterpret_cast<unsigned*>(c->d_ext + tab_b);
-    unsigned* d_toff = reinterpret_cast<unsigned*>(c->d_ext + tab_b + cnt_b);
-    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b);
-    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b + blk_b);
-    unsigned long long* d_offs = reinterpret_cast<unsigned long long*>(c->d_ext + tab_b + cnt_b + toff_b + 2 * blk_b);
-    long long* d_cut = reinterpret_cast<long long*>(c->d_ext + tab_b + cnt_b + toff_b + 2 * blk_b + offs_b);
-
-    ExtractIn in;
-    in.tab = d_tab;
-    in.n = n;
-    in.pool = c->pool;
-    in.chk = source ? c->chk : nullptr;
-    in.act = c->d_act;
-    in.xyz = c->xyz;
-    in.rec = c->rec;
-    in.P = c->P;
-    in.W = c->W;
-    in.sig_max = ext_float_floor(max_sigma);
-    in.rho_min = ext_float_floor(min_rho);
-    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, sizeof(ExtractSlot) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_cnt);
-    scan_counts(c, d_cnt, nt, d_toff, d_bsum, d_boff);
-    hipLaunchKernelGGL(k_extract_offsets, dim3(blocks_for(n + 1)), dim3(BLOCK), 0, c->stream, d_tab, n, nt, d_toff, d_boff,
-                       d_offs);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_offs, d_offs, sizeof(unsigned long long) * (size_t)(n + 1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the one wait in the middle: the total sizes what follows
-    for (int i = 0; i <= n; i++) offsets[i] = (long long)h_offs[i];
-    const long long total = offsets[n];
-    if (st) st->total = total, st->d_offsets = d_offs;
-    if (!st && total > out->capacity) return fail(SDM_EINVAL, "capacity " + std::to_string(out->capacity) + " < " +
-                                                           std::to_string(total) + " points (offsets filled)");
-    if (total == 0) return SDM_OK;
-
-    // where pass 3 writes: the caller's device buffers, or one staging region per requested field (the pixel codes are
-    // staged for k_point_support when the caller did not ask for them)
-    ExtractOut dst;
-    unsigned long long* d_sup = nullptr;
-    const bool stage_all = st || !out->on_device;
-    const bool stage_pix = w_sup && !out->pixel;
-    size_t xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, sup_off = 0;
-    {
-        const size_t t = (size_t)total;
-        size_t at = 0;
-        if (stage_all && w_xyz) xyz_off = at, at += ext_align(12 * t);
-        if ((stage_all && w_pix) || stage_pix) pix_off = at, at += ext_align(4 * t);
-        if (stage_all && w_rs) rs_off = at, at += ext_align(8 * t);
-        if (stage_all && w_im) im_off = at, at += ext_align(t);
-        if (stage_all && w_sup) sup_off = at, at += ext_align(8 * t);
-        if (at && (rc = ext_grow_dev(&c->d_ext_stage, &c->ext_stage_bytes, at))) return rc;
-    }
-    unsigned char* b = c->d_ext_stage;
-    if (!stage_all) {
-        dst.xyz = out->xyz;
-        dst.pixel = stage_pix ? reinterpret_cast<unsigned*>(b + pix_off) : out->pixel;
-        dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
-        dst.intensity = out->intensity;
-        d_sup = support;
-    } else {
-        dst.xyz = w_xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
-        dst.pixel = (w_pix || stage_pix) ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
-        dst.rho_sigma = w_rs ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
-        dst.intensity = w_im ? b + im_off : nullptr;
-        d_sup = w_sup ? reinterpret_cast<unsigned long long*>(b + sup_off) : nullptr;
-    }
-    hipLaunchKernelGGL(k_extract_write, dim3((unsigned)nt), dim3(BLOCK), 0, c->stream, in, d_toff, d_boff, dst);
-    HIP_TRY(hipGetLastError());
-    if (w_sup) {
-        long long blocks = 0;
-        for (int i = 0; i < n; i++) {
-            h_cut[i] = blocks;
-            blocks += (offsets[i + 1] - offsets[i] + SUP_BLOCK - 1) / SUP_BLOCK;
-        }
-        h_cut[n] = blocks;
-        HIP_TRY(hipMemcpyAsync(d_cut, h_cut, sizeof(long long) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
-        launch_sliced(c, blocks, [&](long long b0, unsigned g) {
-            hipLaunchKernelGGL(k_point_support, dim3(g), dim3(SUP_BLOCK), 0, c->stream, c->pool, c->P, c->d_refs, c->d_pairs, n,
-                               n_nbr, c->W, c->H, d_cut, b0, d_offs, dst.pixel, d_sup);
-        }, SUP_BLOCK);
-        HIP_TRY(hipGetLastError());
-        if (st) st->d_support = d_sup, st->d_block0 = d_cut, st->blocks = blocks;
-    }
-    if (st) {
-        st->at = dst;
-        return SDM_OK;
-    }
-    if (!out->on_device) {
-        const size_t t = (size_t)total;
-        if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, dst.xyz, 12 * t, hipMemcpyDeviceToHost, c->stream));
-        if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, dst.pixel, 4 * t, hipMemcpyDeviceToHost, c->stream));
-        if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, dst.rho_sigma, 8 * t, hipMemcpyDeviceToHost, c->stream));
-        if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, dst.intensity, t, hipMemcpyDeviceToHost, c->stream));
-        if (support) HIP_TRY(hipMemcpyAsync(support, d_sup, 8 * t, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SDM_OK;
-}
-
-int sdm_extract_points(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
-                       sdm_point_buffers* out, long long* offsets)
-{
-    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
-    if (!out->xyz && !out->pixel && !out->rho_sigma && !out->intensity) return fail(SDM_EINVAL, "no output field requested");
-    return extract_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, out, nullptr, offsets);
-}
-
-int sdm_extract_points_support(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
-                               double max_sigma, double min_rho, sdm_point_buffers* out, unsigned long long* support,
-                               long long* offsets)
-{
-    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
-    if (!support) return fail(SDM_EINVAL, "null support");
-    if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
-    return extract_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, out, support, offsets);
-}
-
-// ---- one point per voxel (sdm_extract_points_voxel, sdm_voxel.h; with `cams` sdm_extract_points_voxel_cameras,
-// sdm_voxcam.h: the neighbour table is read only then; with `fs` also sdm_extract_points_voxel_freespace, sdm_carve.h:
-// the lists and the kept points' xyz are then formed on the device whether the caller takes them or not) -----------------
-static int voxel_core(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source, double max_sigma,
-                      double min_rho, float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox,
-                      sdm_voxel_cameras* cams, sdm_voxel_freespace* fs, long long* offsets)
-{
-    if (!c || !out || !offsets) return fail(SDM_EINVAL, "null argument");
-    if (n < 0) return fail(SDM_EINVAL, "null or negative slot list");
-    if (cams) {
-        if (!nbr_slots) return fail(SDM_EINVAL, "null nbr_slots");
-        if (!fs && !cams->cam_offsets && !cams->cam_slots) return fail(SDM_EINVAL, "no camera output requested");
-        if (cams->cam_slots && cams->cam_capacity < 0) return fail(SDM_EINVAL, "negative capacity");
-        if (out->on_device && ((uintptr_t)cams->cam_offsets % 8 || (uintptr_t)cams->cam_slots % 4))
-            return fail(SDM_EINVAL, "device buffer not aligned (cam_offsets: 8 B; cam_slots: 4 B)");
-    }
-    if (fs && out->on_device && (uintptr_t)fs->crossings % 4) return fail(SDM_EINVAL, "device buffer not aligned (crossings: 4 B)");
-    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size)) return fail(SDM_EINVAL, "voxel_size must be finite and > 0");
-    const float inv = 1.0f / voxel_size;
-    if (!std::isfinite(inv)) return fail(SDM_EINVAL, "1 / voxel_size is not finite");
-    unsigned* mult = vox ? vox->multiplicity : nullptr;
-    unsigned* sidx = vox ? vox->source_index : nullptr;
-    unsigned* repr = vox ? vox->representative : nullptr;
-    if (!cams && !out->xyz && !out->pixel && !out->rho_sigma && !out->intensity && !mult && !sidx && !repr)
-        return fail(SDM_EINVAL, "no output requested");
-    if (out->capacity < 0 || (repr && vox->rep_capacity < 0)) return fail(SDM_EINVAL, "negative capacity");
-    if (out->on_device && (((uintptr_t)out->xyz | (uintptr_t)out->pixel | (uintptr_t)mult | (uintptr_t)sidx | (uintptr_t)repr) % 4 ||
-                           (uintptr_t)out->rho_sigma % 8))
-        return fail(SDM_EINVAL, "device buffer not aligned (xyz, pixel, multiplicity, source_index, representative: 4 B; "
-                                "rho_sigma: 8 B)");
-
-    // the plain cloud into the staging (xyz and rho_sigma feed the merge whatever the caller asks for)
-    ExtractStaged st{};
-    st.pixel = out->pixel != nullptr;
-    st.intensity = out->intensity != nullptr;
-    st.support = cams != nullptr;
-    sdm_point_buffers none{};
-    std::vector<long long> plain((size_t)n + 1, 0);
-    int rc = extract_core(c, n, slots, cams ? n_nbr : 0, cams ? nbr_slots : nullptr, source, max_sigma, min_rho, &none,
-                          nullptr, plain.data(), &st);
-    if (rc) return rc;
-    const long long T = st.total;
-    if (vox) vox->plain_total = T;
-    if (T >= 0xffffffffll) return fail(SDM_EINVAL, "2^32 - 1 or more plain points in one call");
-    if (T == 0) {  // (extract_core has waited for the stream)
-        for (int i = 0; i <= n; i++) offsets[i] = 0;
-        if (cams && cams->cam_offsets) {  // no kept point: the one entry cam_offsets[0] = 0
-            if (out->on_device) {
-                HIP_TRY(hipMemsetAsync(cams->cam_offsets, 0, sizeof(long long), c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-            } else {
-                cams->cam_offsets[0] = 0;
-            }
-        }
-        return SDM_OK;
-    }
-    unsigned long long cap = 1024;
-    while (cap < 2ull * (unsigned long long)T) cap <<= 1;
-    if (cap > (1ull << 31)) return fail(SDM_EINVAL, "more than 2^30 plain points: the voxel table would exceed 2^31 slots");
-
-    const long long vt = (T + EXT_TILE - 1) / EXT_TILE;
-    const long long vb = (vt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    const size_t key_b = 8 * (size_t)cap, cnt_b = 4 * (size_t)cap + 256 /* + the overflow flag */, rank_b = 4 * (size_t)cap;
-    const size_t where_b = ext_align(4 * (size_t)T), tcnt_b = ext_align(4 * (size_t)vt), toff_b = ext_align(4 * (size_t)(vt + 1));
-    const size_t blk_b = ext_align(8 * (size_t)vb), offs_b = ext_align(8 * (size_t)(n + 2));
-    if ((rc = ext_grow_dev(&c->d_vox, &c->vox_bytes, 2 * key_b + cnt_b + rank_b + where_b + tcnt_b + toff_b + 2 * blk_b + offs_b)))
-        return rc;
-    if ((rc = ext_grow_host(&c->h_ext, &c->ext_host_bytes, offs_b))) return rc;  // (the plain passes are done with it)
-    unsigned char* p = c->d_vox;
-    VoxTable tb;
-    tb.keys = reinterpret_cast<unsigned long long*>(p), p += key_b;
-    tb.vals = reinterpret_cast<unsigned long long*>(p), p += key_b;
-    tb.cnt = reinterpret_cast<unsigned*>(p);
-    unsigned* d_flag = reinterpret_cast<unsigned*>(p + 4 * (size_t)cap);
-    p += cnt_b;
-    tb.rank = reinterpret_cast<unsigned*>(p), p += rank_b;
-    tb.mask = cap - 1;
-    unsigned* d_where = reinterpret_cast<unsigned*>(p);
-    p += where_b;
-    unsigned* d_tcnt = reinterpret_cast<unsigned*>(p);
-    p += tcnt_b;
-    unsigned* d_toff = reinterpret_cast<unsigned*>(p);
-    p += toff_b;
-    unsigned long long* d_bsum = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_boff = reinterpret_cast<unsigned long long*>(p);
-    p += blk_b;
-    unsigned long long* d_voffs = reinterpret_cast<unsigned long long*>(p);
-    unsigned long long* h_voffs = reinterpret_cast<unsigned long long*>(c->h_ext);
-
-    HIP_TRY(hipMemsetAsync(tb.keys, 0xff, 2 * key_b, c->stream));  // keys: VOX_EMPTY; values: the minimum's identity
-    HIP_TRY(hipMemsetAsync(tb.cnt, 0, cnt_b, c->stream));           // counts and the flag
-    const long long pblocks = (T + BLOCK - 1) / BLOCK;
-    launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
-        hipLaunchKernelGGL(k_voxel_insert, dim3(g), dim3(BLOCK), 0, c->stream, st.at.xyz, st.at.rho_sigma, T, b0 * BLOCK, inv, tb,
-                           d_where, d_flag);
-    });
-    launch_sliced(c, vt, [&](long long t0, unsigned g) {
-        hipLaunchKernelGGL(k_voxel_count, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0, d_tcnt);
-    });
-    scan_counts(c, d_tcnt, vt, d_toff, d_bsum, d_boff);
-    hipLaunchKernelGGL(k_voxel_offsets, dim3((unsigned)(n + 2)), dim3(BLOCK), 0, c->stream, tb, d_where, T, st.d_offsets, n, vt,
-                       d_toff, d_boff, d_flag, d_voffs);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_voffs, d_voffs, 8 * (size_t)(n + 2), hipMemcpyDeviceToHost, c->stream));
-    // the camera table (sdm_voxcam.h), built while the passes run: the distinct slots of the call in ascending order, and
-    // per row the camera index of its own slot and of its neighbours (extract_core has checked every slot's range);
-    // h_vcam = the total E read back | slot_of_cam[Cn] own_cam[n] nbr_cam[n][n_nbr]
-    int Cn = 0;
-    size_t cam_tab_n = 0;
-    if (cams) {
-        const size_t np = (size_t)n * (size_t)n_nbr;
-        std::vector<int> cam_of((size_t)c->cfg.max_keyframes, -1);
-        for (int i = 0; i < n; i++) cam_of[(size_t)slots[i]] = 0;
-        for (size_t i = 0; i < np; i++) cam_of[(size_t)nbr_slots[i]] = 0;
-        for (int s = 0; s < c->cfg.max_keyframes; s++)
-            if (cam_of[(size_t)s] == 0) cam_of[(size_t)s] = Cn++;
-        cam_tab_n = (size_t)Cn + (size_t)n + np;
-        if ((rc = ext_grow_host(&c->h_vcam, &c->vcam_host_bytes, 256 + ext_align(4 * cam_tab_n) + (fs ? 16 * (size_t)Cn : 0))))
-            return rc;
-        int* h_tab = reinterpret_cast<int*>(c->h_vcam + 256);
-        for (int s = 0; s < c->cfg.max_keyframes; s++)
-            if (cam_of[(size_t)s] >= 0) h_tab[cam_of[(size_t)s]] = s;
-        for (int i = 0; i < n; i++) h_tab[Cn + i] = cam_of[(size_t)slots[i]];
-        for (size_t i = 0; i < np; i++) h_tab[(size_t)Cn + (size_t)n + i] = cam_of[(size_t)nbr_slots[i]];
-        if (fs) {  // the camera centres from the current poses, as pointset_pixel forms Ow: O = -(Rwc * tcw)
-            float* h_org = reinterpret_cast<float*>(c->h_vcam + 256 + ext_align(4 * cam_tab_n));
-            for (int q = 0; q < Cn; q++) {
-                const float* Tcw = c->h_meta[h_tab[q]].Tcw;
-                float Rwc[9], Ow[3];
-                const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
-                for (int i = 0; i < 3; i++)
-                    for (int k = 0; k < 3; k++) Rwc[i * 3 + k] = Tcw[k * 4 + i];
-                mat3_vec(Rwc, tcw, Ow);
-                for (int i = 0; i < 3; i++) h_org[q * 4 + i] = -Ow[i];
-                h_org[q * 4 + 3] = 0.f;
-            }
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the kept total sizes what follows
-    if (h_voffs[n + 1]) return fail(SDM_EHIP, "voxel table overflow");
-    for (int i = 0; i <= n; i++) offsets[i] = (long long)h_voffs[i];
-    const long long M = offsets[n];
-    if (M > out->capacity) return fail(SDM_EINVAL, "capacity " + std::to_string(out->capacity) + " < " + std::to_string(M) +
-                                                       " points (offsets and plain_total filled)");
-    if (repr && T > vox->rep_capacity)
-        return fail(SDM_EINVAL, "rep_capacity " + std::to_string(vox->rep_capacity) + " < " + std::to_string(T) +
-                                    " plain points (offsets and plain_total filled)");
-
-    // where the kept points go: the caller's device buffers, or one staging region per requested output
-    ExtractOut dst;
-    unsigned *d_mult = mult, *d_sidx = sidx, *d_repr = repr;
-    if (out->on_device) {
-        dst.xyz = out->xyz;
-        dst.pixel = out->pixel;
-        dst.rho_sigma = reinterpret_cast<float2*>(out->rho_sigma);
-        dst.intensity = out->intensity;
-    } else {
-        const size_t m = (size_t)M;
-        size_t at = 0, xyz_off = 0, pix_off = 0, rs_off = 0, im_off = 0, mult_off = 0, sidx_off = 0, repr_off = 0;
-        if (out->xyz) xyz_off = at, at += ext_align(12 * m);
-        if (out->pixel) pix_off = at, at += ext_align(4 * m);
-        if (out->rho_sigma) rs_off = at, at += ext_align(8 * m);
-        if (out->intensity) im_off = at, at += ext_align(m);
-        if (mult) mult_off = at, at += ext_align(4 * m);
-        if (sidx) sidx_off = at, at += ext_align(4 * m);
-        if (repr) repr_off = at, at += ext_align(4 * (size_t)T);
-        if ((rc = ext_grow_dev(&c->d_vox_out, &c->vox_out_bytes, at))) return rc;
-        unsigned char* b = c->d_vox_out;
-        dst.xyz = out->xyz ? reinterpret_cast<float*>(b + xyz_off) : nullptr;
-        dst.pixel = out->pixel ? reinterpret_cast<unsigned*>(b + pix_off) : nullptr;
-        dst.rho_sigma = out->rho_sigma ? reinterpret_cast<float2*>(b + rs_off) : nullptr;
-        dst.intensity = out->intensity ? b + im_off : nullptr;
-        d_mult = mult ? reinterpret_cast<unsigned*>(b + mult_off) : nullptr;
-        d_sidx = sidx ? reinterpret_cast<unsigned*>(b + sidx_off) : nullptr;
-        d_repr = repr ? reinterpret_cast<unsigned*>(b + repr_off) : nullptr;
-    }
-    // (fs) the centres, the call totals, and the kept points' xyz when no destination holds them on the device
-    float* d_org = nullptr;
-    unsigned long long* d_fs_tot = nullptr;
-    if (fs) {
-        const size_t org_b = ext_align(16 * (size_t)Cn), xyz_at = org_b + 256;
-        if ((rc = ext_grow_dev(&c->d_carve, &c->carve_bytes, xyz_at + (dst.xyz ? 0 : 12 * (size_t)M)))) return rc;
-        d_org = reinterpret_cast<float*>(c->d_carve);
-        d_fs_tot = reinterpret_cast<unsigned long long*>(c->d_carve + org_b);
-        if (!dst.xyz) dst.xyz = reinterpret_cast<float*>(c->d_carve + xyz_at);
-    }
-    // (cams) scratch: the staged camera table, every plain point's kept rank when the caller takes no `representative`,
-    // the bitsets, the tile counts and their scan; grown before anything that reads it is queued
-    unsigned* d_rank = d_repr;
-    const int Wd = (Cn + 63) / 64;
-    const long long kt = (M + EXT_TILE - 1) / EXT_TILE;
-    const long long kb = (kt + 1 + EXT_SCAN - 1) / EXT_SCAN;
-    VoxCamTable ctab{};
-    unsigned long long *d_bits = nullptr, *d_kbsum = nullptr, *d_kboff = nullptr, *d_E = nullptr;
-    unsigned *d_ktcnt = nullptr, *d_ktoff = nullptr;
-    if (cams) {
-        // the scan keeps 32-bit sums per EXT_SCAN tiles (k_extract_scan_tiles): a kept point has at most Cn cameras
-        if ((unsigned long long)std::min(M, (long long)EXT_TILE * EXT_SCAN) * (unsigned long long)Cn >= (1ull << 32))
-            return fail(SDM_EINVAL, "camera lists of 2^22 kept points could pass 2^32 entries: too many distinct slots in one call");
-        const size_t tab_b = ext_align(4 * cam_tab_n), rank_b = d_repr ? 0 : ext_align(4 * (size_t)T);
-        const size_t bits_b = ext_align(8 * (size_t)M * (size_t)Wd), ktcnt_b = ext_align(4 * (size_t)kt);
-        const size_t ktoff_b = ext_align(4 * (size_t)(kt + 1)), kblk_b = ext_align(8 * (size_t)kb);
-        if ((rc = ext_grow_dev(&c->d_vcam, &c->vcam_bytes, tab_b + rank_b + bits_b + ktcnt_b + ktoff_b + 2 * kblk_b + 256)))
-            return rc;
-        unsigned char* q = c->d_vcam;
-        int* d_ctab = reinterpret_cast<int*>(q);
-        q += tab_b;
-        if (!d_repr) d_rank = reinterpret_cast<unsigned*>(q);
-        q += rank_b;
-        d_bits = reinterpret_cast<unsigned long long*>(q), q += bits_b;
-        d_ktcnt = reinterpret_cast<unsigned*>(q), q += ktcnt_b;
-        d_ktoff = reinterpret_cast<unsigned*>(q), q += ktoff_b;
-        d_kbsum = reinterpret_cast<unsigned long long*>(q), q += kblk_b;
-        d_kboff = reinterpret_cast<unsigned long long*>(q), q += kblk_b;
-        d_E = reinterpret_cast<unsigned long long*>(q);
-        ctab.slot_of_cam = d_ctab;
-        ctab.own_cam = d_ctab + Cn;
-        ctab.nbr_cam = d_ctab + Cn + n;
-        HIP_TRY(hipMemsetAsync(d_bits, 0, 8 * (size_t)M * (size_t)Wd, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_ctab, c->h_vcam + 256, 4 * cam_tab_n, hipMemcpyHostToDevice, c->stream));
-        if (fs)
-            HIP_TRY(hipMemcpyAsync(d_org, c->h_vcam + 256 + ext_align(4 * cam_tab_n), 16 * (size_t)Cn, hipMemcpyHostToDevice,
-                                   c->stream));
-    }
-    launch_sliced(c, vt, [&](long long t0, unsigned g) {
-        hipLaunchKernelGGL(k_voxel_write, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, t0, d_toff, d_boff, st.at, dst,
-                           d_mult, d_sidx, d_rank);
-    });
-    if (d_rank)
-        launch_sliced(c, pblocks, [&](long long b0, unsigned g) {
-            hipLaunchKernelGGL(k_voxel_rep, dim3(g), dim3(BLOCK), 0, c->stream, tb, d_where, T, b0 * BLOCK, d_rank);
-        });
-    HIP_TRY(hipGetLastError());
-    if (cams) {
-        // SDM_VOXCAM_PLAIN_OR: one atomic per lane and word instead of one per run of equal rank (A/B; the same bits)
-        const bool plain_or = getenv("SDM_VOXCAM_PLAIN_OR") != nullptr;
-        launch_sliced(c, st.blocks, [&](long long b0, unsigned g) {
-            if (plain_or)
-                hipLaunchKernelGGL(k_voxcam_or<false>, dim3(g), dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
-                                   st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
-            else
-                hipLaunchKernelGGL(k_voxcam_or<true>, dim3(g), dim3(SUP_BLOCK), 0, c->stream, st.d_block0, b0, n, n_nbr,
-                                   st.d_offsets, st.d_support, d_rank, ctab, Wd, d_bits);
-        }, SUP_BLOCK);
-        launch_sliced(c, kt, [&](long long t0, unsigned g) {
-            hipLaunchKernelGGL(k_voxcam_count, dim3(g), dim3(BLOCK), 0, c->stream, d_bits, Wd, M, t0, d_ktcnt);
-        });
-        scan_counts(c, d_ktcnt, kt, d_ktoff, d_kbsum, d_kboff);
-        // (with no slot, k_extract_offsets writes the one entry offsets[0] = the offset of tile kt: the total)
-        hipLaunchKernelGGL(k_extract_offsets, dim3(1), dim3(BLOCK), 0, c->stream, (const ExtractSlot*)nullptr, 0, kt, d_ktoff,
-                           d_kboff, d_E);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->h_vcam, d_E, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));  // the third wait: the lists' total, for the capacity check
-        const long long E = (long long)*reinterpret_cast<unsigned long long*>(c->h_vcam);
-        cams->cam_total = E;
-        if (cams->cam_slots && E > cams->cam_capacity)
-            return fail(SDM_EINVAL, "cam_capacity " + std::to_string(cams->cam_capacity) + " < " + std::to_string(E) +
-                                        " list entries (offsets, plain_total and cam_total filled)");
-        if (fs && E >= (1ll << 32)) return fail(SDM_EINVAL, "2^32 or more rays in one call");
-        long long* d_coff = cams->cam_offsets;
-        int* d_cslots = cams->cam_slots;
-        unsigned* d_cross = fs ? fs->crossings : nullptr;
-        if (!out->on_device || fs) {
-            // on the device: the caller's arrays, and with fs whatever of the lists it did not name; else a staging region
-            // per requested output (with fs: both lists and the counters)
-            const bool s_off = fs ? !(out->on_device && cams->cam_offsets) : cams->cam_offsets != nullptr;
-            const bool s_slots = fs ? !(out->on_device && cams->cam_slots) : cams->cam_slots != nullptr;
-            const size_t off_b = s_off ? ext_align(8 * (size_t)(M + 1)) : 0;
-            const size_t slots_b = s_slots ? ext_align(4 * (size_t)E) : 0;
-            const size_t cross_b = (fs && !out->on_device) ? 4 * (size_t)M : 0;
-            if ((rc = ext_grow_dev(&c->d_vcam_out, &c->vcam_out_bytes, off_b + slots_b + cross_b))) return rc;
-            if (s_off) d_coff = reinterpret_cast<long long*>(c->d_vcam_out);
-            else if (!out->on_device) d_coff = nullptr;
-            if (s_slots) d_cslots = reinterpret_cast<int*>(c->d_vcam_out + off_b);
-            else if (!out->on_device) d_cslots = nullptr;
-            if (cross_b) d_cross = reinterpret_cast<unsigned*>(c->d_vcam_out + off_b + slots_b);
-        }
-        launch_sliced(c, kt, [&](long long t0, unsigned g) {
-            hipLaunchKernelGGL(k_voxcam_write, dim3(g), dim3(BLOCK), 0, c->stream, d_bits, Wd, M, t0, d_ktoff, d_kboff,
-                               ctab.slot_of_cam, d_coff, d_cslots);
-        });
-        HIP_TRY(hipGetLastError());
-        if (fs) {  // sdm_carve.h: one lane per list entry walks its ray through the table
-            HIP_TRY(hipMemsetAsync(d_cross, 0, 4 * (size_t)M, c->stream));
-            HIP_TRY(hipMemsetAsync(d_fs_tot, 0, 16, c->stream));
-            CarveIn in;
-            in.xyz = dst.xyz;
-            in.cam_offsets = d_coff;
-            in.cam_slots = d_cslots;
-            in.slot_of_cam = ctab.slot_of_cam;
-            in.origin = d_org;
-            in.M = M;
-            in.E = E;
-            in.Cn = Cn;
-            in.voxel = voxel_size;
-            in.inv = inv;
-            in.end_margin = fs->end_margin;
-            in.max_steps = fs->max_steps;
-            const long long eblocks = (E + BLOCK - 1) / BLOCK;
-            launch_sliced(c, eblocks, [&](long long b0, unsigned g) {
-                hipLaunchKernelGGL(k_voxel_carve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, tb, d_cross, d_fs_tot);
-            });
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(c->h_vcam + 16, d_fs_tot, 16, hipMemcpyDeviceToHost, c->stream));
-            if (!out->on_device) HIP_TRY(hipMemcpyAsync(fs->crossings, d_cross, 4 * (size_t)M, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (!out->on_device) {
-            if (cams->cam_offsets)
-                HIP_TRY(hipMemcpyAsync(cams->cam_offsets, d_coff, 8 * (size_t)(M + 1), hipMemcpyDeviceToHost, c->stream));
-            if (cams->cam_slots && E > 0)
-                HIP_TRY(hipMemcpyAsync(cams->cam_slots, d_cslots, 4 * (size_t)E, hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    if (!out->on_device) {
-        const size_t m = (size_t)M;
-        if (out->xyz) HIP_TRY(hipMemcpyAsync(out->xyz, dst.xyz, 12 * m, hipMemcpyDeviceToHost, c->stream));
-        if (out->pixel) HIP_TRY(hipMemcpyAsync(out->pixel, dst.pixel, 4 * m, hipMemcpyDeviceToHost, c->stream));
-        if (out->rho_sigma) HIP_TRY(hipMemcpyAsync(out->rho_sigma, dst.rho_sigma, 8 * m, hipMemcpyDeviceToHost, c->stream));
-        if (out->intensity) HIP_TRY(hipMemcpyAsync(out->intensity, dst.intensity, m, hipMemcpyDeviceToHost, c->stream));
-        if (mult) HIP_TRY(hipMemcpyAsync(mult, d_mult, 4 * m, hipMemcpyDeviceToHost, c->stream));
-        if (sidx) HIP_TRY(hipMemcpyAsync(sidx, d_sidx, 4 * m, hipMemcpyDeviceToHost, c->stream));
-        if (repr) HIP_TRY(hipMemcpyAsync(repr, d_repr, 4 * (size_t)T, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the last wait
-    if (fs) {
-        const unsigned long long* tot = reinterpret_cast<const unsigned long long*>(c->h_vcam + 16);
-        fs->rays_total = cams->cam_total;
-        fs->rays_skipped = (long long)tot[0];
-        fs->cells_visited = (long long)tot[1];
-    }
-    return SDM_OK;
-}
-
-int sdm_extract_points_voxel(sdm_ctx* c, int n, const int* slots, int source, double max_sigma, double min_rho,
-                             float voxel_size, sdm_point_buffers* out, sdm_voxel_buffers* vox, long long* offsets)
-{
-    return voxel_core(c, n, slots, 0, nullptr, source, max_sigma, min_rho, voxel_size, out, vox, nullptr, nullptr, offsets);
-}
-
-int sdm_extract_points_voxel_cameras(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
-                                     double max_sigma, double min_rho, float voxel_size, sdm_point_buffers* out,
-                                     sdm_voxel_buffers* vox, sdm_voxel_cameras* cams, long long* offsets)
-{
-    if (!cams) return fail(SDM_EINVAL, "null cams");
-    cams->cam_total = 0;
-    return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, nullptr, offsets);
-}
-
-int sdm_extract_points_voxel_freespace(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nbr_slots, int source,
-                                       double max_sigma, double min_rho, float voxel_size, sdm_point_buffers* out,
-                                       sdm_voxel_buffers* vox, sdm_voxel_cameras* cams, sdm_voxel_freespace* fs,
-                                       long long* offsets)
-{
-    if (fs) fs->rays_total = fs->rays_skipped = fs->cells_visited = 0;
-    if (!cams) return fail(SDM_EINVAL, "null cams");
-    cams->cam_total = 0;
-    if (!fs) return fail(SDM_EINVAL, "null fs");
-    if (!fs->crossings) return fail(SDM_EINVAL, "null crossings");
-    if (fs->end_margin < 0) return fail(SDM_EINVAL, "negative end_margin");
-    if (fs->max_steps < 1 || fs->max_steps > SDM_FREESPACE_MAX_STEPS)
-        return fail(SDM_EINVAL, "max_steps outside 1 .. SDM_FREESPACE_MAX_STEPS");
-    return voxel_core(c, n, slots, n_nbr, nbr_slots, source, max_sigma, min_rho, voxel_size, out, vox, cams, fs, offsets);
-}
+// ---- the host steps that belong to no call; the point-cloud calls (sdm_extract_bound, sdm_extract_points*, extract_core) ------
+#include "sdm_host_steps.h"
+#include "sdm_extract_host.h"
 
 // ---- the persistent voxel map: every sdm_vmap_* call and the steps they share ---------------------------------------------
 #include "sdm_vmap_host.h"

@@ -1,63 +1,13 @@
 // sdm_vmap_host.h -- the host side of the persistent voxel map: every sdm_vmap_* call of the C ABI (the kernels are in
 // sdm_vmap*.h, one header per feature) and the steps the calls share.  Included by sdm_engine.hip inside its extern "C"
-// block, after sdm_ctx, fail, HIP_TRY, launch_sliced, scan_counts, the ext_* helpers and extract_core are defined (one
-// translation unit).  DESIGN.md, "The voxel map's host code", says how a call is put together from the steps.
+// block after sdm_ctx, fail, HIP_TRY, launch_sliced and scan_counts, after sdm_host_steps.h (the ext_* helpers, DevBlock, Carver,
+// carve_scratch, Scan, stage_in) and sdm_extract_host.h (extract_core, call_cameras, slot_centre).  DESIGN.md §24 says how a call is built.
 #pragma once
 
 extern "C++" {
 namespace {
 
-// ---- the shared steps: device blocks, scratch, layouts -------------------------------------------------------------------
-// move-only owner of one hipMalloc block.  A call makes its new blocks in owners and installs them in the context once
-// everything has succeeded; whatever an owner holds when it leaves -- a block never installed, or the context's old one
-// after install -- is freed.
-struct DevBlock {
-    unsigned char* p = nullptr;
-    DevBlock() = default;
-    DevBlock(DevBlock&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBlock(const DevBlock&) = delete;
-    DevBlock& operator=(const DevBlock&) = delete;
-    ~DevBlock() { (void)hipFree(p); }
-    int alloc(size_t bytes)
-    {
-        HIP_TRY(hipMalloc((void**)&p, bytes));
-        return SDM_OK;
-    }
-    void install(unsigned char*& slot) { std::swap(slot, p); }
-};
-
-// bump allocator over 256-byte-aligned regions of one buffer.  Over a null base it only adds up the bytes.
-struct Carver {
-    unsigned char* base;
-    size_t at = 0;
-    template <typename T>
-    T* ptr(size_t offset) const
-    {
-        return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + offset);
-    }
-    template <typename T>
-    T* take(size_t count)
-    {
-        T* r = ptr<T>(at);
-        at += ext_align(sizeof(T) * count);
-        return r;
-    }
-};
-
-// A call describes its scratch once, as describe(Carver&): run over a null base for the bytes `buf` must hold, then over
-// the grown buffer for the pointers, so the sum and the walk cannot disagree.
-template <typename F>
-int carve_scratch(unsigned char** buf, size_t* have, F&& describe)
-{
-    Carver bytes{nullptr};
-    describe(bytes);
-    const int rc = ext_grow_dev(buf, have, bytes.at);
-    if (rc) return rc;
-    Carver k{*buf};
-    describe(k);
-    return SDM_OK;
-}
-
+// ---- the shared steps: scratch and layouts (DevBlock, Carver, carve_scratch, Scan, stage_in: sdm_host_steps.h) --------------
 // the 512 B every scratch starts with: the counters a call clears and its kernels fill
 struct ScratchHead {
     unsigned char* base = nullptr;
@@ -74,22 +24,6 @@ struct ScratchHead {
         tot = k.ptr<unsigned long long>(at + 256);
     }
 };
-
-// tiles of EXT_TILE items: the unit the count and commit kernels work in
-long long ext_tiles(long long items) { return (items + EXT_TILE - 1) / EXT_TILE; }
-
-// per-tile counts and the arrays of their scan (scan_counts)
-struct Scan {
-    unsigned *cnt = nullptr, *off = nullptr;
-    unsigned long long *bsum = nullptr, *boff = nullptr;
-    Scan() = default;
-    Scan(Carver& k, long long tiles)
-        : cnt(k.take<unsigned>((size_t)tiles)), off(k.take<unsigned>((size_t)tiles + 1)),
-          bsum(k.take<unsigned long long>((size_t)scan_blocks(tiles))), boff(k.take<unsigned long long>((size_t)scan_blocks(tiles)))
-    {
-    }
-};
-void scan_counts(sdm_ctx* c, const Scan& s, long long tiles) { scan_counts(c, s.cnt, tiles, s.off, s.bsum, s.boff); }
 
 // two of them over the same tiles, interleaved: cnt | cnt | off | off | bsum | boff | bsum | boff
 struct ScanPair {
@@ -133,12 +67,6 @@ struct VobsScratch {
     {
     }
 };
-
-// a host source into its staging region (which the kernels read through pointers to const)
-hipError_t stage_in(sdm_ctx* c, const void* dst, const void* src, size_t bytes)
-{
-    return hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, c->stream);
-}
 
 int memset_rc(hipError_t e)
 {
@@ -763,13 +691,7 @@ int sdm_vmap_carve(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nb
     // the cameras of the call: its distinct slots in ascending order, and per slot i the distinct neighbours other than
     // slots[i], in the order of their first column, each with the mask of the columns that name it (extract_core has
     // checked every slot's range; n_nbr <= 64)
-    std::vector<int> cam_of((size_t)c->cfg.max_keyframes, -1);
-    for (int i = 0; i < n; i++) cam_of[(size_t)slots[i]] = 0;
-    for (size_t i = 0; i < (size_t)n * (size_t)n_nbr; i++) cam_of[(size_t)nbr_slots[i]] = 0;
-    int Cn = 0;
-    std::vector<int> slot_of_cam;
-    for (int s = 0; s < c->cfg.max_keyframes; s++)
-        if (cam_of[(size_t)s] == 0) cam_of[(size_t)s] = Cn++, slot_of_cam.push_back(s);
+    const CallCameras cam = call_cameras(c, n, slots, n_nbr, nbr_slots);
     std::vector<std::vector<std::pair<int, unsigned long long>>> lists((size_t)n);
     int D = 0;
     for (int i = 0; i < n; i++) {
@@ -793,62 +715,44 @@ int sdm_vmap_carve(sdm_ctx* c, int n, const int* slots, int n_nbr, const int* nb
         evid.install(v.d_evid);
         v.crossings = cr, v.ends = en;
     }
+    // the totals at +256 of the scratch's head and of the pinned mirror's; behind each head the same table, which goes over
+    // in one copy: the centres | per slot its own camera | per slot and list place the camera | and its columns
     const size_t nd = (size_t)n * (size_t)D;
-    const size_t org_b = ext_align(16 * (size_t)Cn), own_b = ext_align(4 * (size_t)n), cam_b = ext_align(4 * nd),
-                 mask_b = ext_align(8 * nd), tab_b = org_b + own_b + cam_b + mask_b;
-    if ((rc = ext_grow_dev(&v.d_scratch, &v.scratch_bytes, 512 + tab_b))) return rc;
-    if ((rc = ext_grow_host(&v.h_pin, &v.pin_bytes, 256 + tab_b))) return rc;
-    unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(v.d_scratch + 256);
-    unsigned char* d_tab = v.d_scratch + 512;
-    unsigned char* h_tab = v.h_pin + 256;
-    float* h_org = reinterpret_cast<float*>(h_tab);
-    int* h_own = reinterpret_cast<int*>(h_tab + org_b);
-    int* h_cam = reinterpret_cast<int*>(h_tab + org_b + own_b);
-    unsigned long long* h_mask = reinterpret_cast<unsigned long long*>(h_tab + org_b + own_b + cam_b);
-    for (int q = 0; q < Cn; q++) {  // the camera centres from the current poses, as pointset_pixel forms Ow: O = -(Rwc * tcw)
-        const float* Tcw = c->h_meta[slot_of_cam[(size_t)q]].Tcw;
-        float Rwc[9], Ow[3];
-        const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
-        for (int i = 0; i < 3; i++)
-            for (int k = 0; k < 3; k++) Rwc[i * 3 + k] = Tcw[k * 4 + i];
-        mat3_vec(Rwc, tcw, Ow);
-        for (int i = 0; i < 3; i++) h_org[q * 4 + i] = -Ow[i];
-        h_org[q * 4 + 3] = 0.f;
-    }
+    struct Table { float* org; int *own, *cam; unsigned long long* mask; size_t bytes; } ht{}, dt{};
+    const auto table = [&](Carver& k, Table& t) {
+        const size_t first = k.at;
+        t.org = k.take<float>(4 * (size_t)cam.Cn);
+        t.own = k.take<int>((size_t)n);
+        t.cam = k.take<int>(nd);
+        t.mask = k.take<unsigned long long>(nd);
+        t.bytes = k.at - first;
+    };
+    ScratchHead head;
+    unsigned long long* h_tot = nullptr;
+    if ((rc = carve_scratch(&v.d_scratch, &v.scratch_bytes, [&](Carver& k) { head = ScratchHead(k), table(k, dt); })) ||
+        (rc = carve_scratch(&v.h_pin, &v.pin_bytes, [&](Carver& k) { h_tot = k.take<unsigned long long>(32), table(k, ht); },
+                            ext_grow_host)))
+        return rc;
+    for (int q = 0; q < cam.Cn; q++) slot_centre(c, cam.slot_of_cam[(size_t)q], ht.org + 4 * q);
     for (int i = 0; i < n; i++) {
-        h_own[i] = cam_of[(size_t)slots[i]];
+        ht.own[i] = cam.cam_of[(size_t)slots[i]];
         const auto& l = lists[(size_t)i];
         for (int d = 0; d < D; d++) {
             const bool have = (size_t)d < l.size();
-            h_cam[(size_t)i * (size_t)D + (size_t)d] = have ? cam_of[(size_t)l[(size_t)d].first] : 0;
-            h_mask[(size_t)i * (size_t)D + (size_t)d] = have ? l[(size_t)d].second : 0ull;
+            ht.cam[(size_t)i * (size_t)D + (size_t)d] = have ? cam.cam_of[(size_t)l[(size_t)d].first] : 0;
+            ht.mask[(size_t)i * (size_t)D + (size_t)d] = have ? l[(size_t)d].second : 0ull;
         }
     }
-    HIP_TRY(hipMemsetAsync(d_tot, 0, 64, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_b, hipMemcpyHostToDevice, c->stream));
-    VmapCarveIn in;
-    in.xyz = st.at.xyz;
-    in.support = D ? st.d_support : nullptr;
-    in.plain_offsets = st.d_offsets;
-    in.origin = reinterpret_cast<const float*>(d_tab);
-    in.own_cam = reinterpret_cast<const int*>(d_tab + org_b);
-    in.nbr_cam = reinterpret_cast<const int*>(d_tab + org_b + own_b);
-    in.nbr_mask = reinterpret_cast<const unsigned long long*>(d_tab + org_b + own_b + cam_b);
-    in.T = T;
-    in.n = n;
-    in.D = D;
-    in.M = (unsigned)v.M;
-    in.voxel = v.voxel_size;
-    in.inv = v.inv;
-    in.end_margin = cv->end_margin;
-    in.max_steps = cv->max_steps;
+    HIP_TRY(hipMemsetAsync(head.tot, 0, 64, c->stream));
+    HIP_TRY(stage_in(c, dt.org, ht.org, dt.bytes));
+    const VmapCarveIn in{st.at.xyz, D ? st.d_support : nullptr, st.d_offsets, dt.own, dt.cam, dt.mask, dt.org, T, n, D, (unsigned)v.M,
+                         v.voxel_size, v.inv, cv->end_margin, cv->max_steps};
     const long long E = ((long long)D + 1) * T;  // candidates, camera-major
     launch_sliced(c, (E + BLOCK - 1) / BLOCK, [&](long long b0, unsigned g) {
-        hipLaunchKernelGGL(k_vmap_carve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, E, v.tb, v.crossings, v.ends, d_tot);
+        hipLaunchKernelGGL(k_vmap_carve, dim3(g), dim3(BLOCK), 0, c->stream, in, b0 * BLOCK, E, v.tb, v.crossings, v.ends, head.tot);
     });
     HIP_TRY(hipGetLastError());
-    unsigned long long* h_tot = reinterpret_cast<unsigned long long*>(v.h_pin);
-    HIP_TRY(hipMemcpyAsync(h_tot, d_tot, 40, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_tot, head.tot, 40, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // the second wait: the end, with the totals
     cv->rays_total = (long long)h_tot[0];
     cv->rays_skipped = (long long)h_tot[1];

@@ -300,6 +300,26 @@ def test_destinations_and_capacity(pkg, engines):
     assert_same(eng.extract_points_voxel_cameras(refs, rows, 0.02, **kw), exp, "sized by the binding")
 
 
+def test_no_plain_point(pkg, engines):
+    """nothing passes the filter: every offset is 0, and the lists are the one entry cam_offsets[0] = 0, on the host and on
+    the device; nothing else is written"""
+    torch = pytest.importorskip("torch")
+    g, eng = engines("plane_64x48_n7")
+    refs, rows = [0, 1, 2], g["nbrs"][[0, 1, 2]]
+    kw = dict(max_sigma=0.3, min_rho=1e30)
+    host = {"xyz": np.full((4, 3), 7.0, np.float32), "cam_offsets": np.full(5, -7, np.int64), "cam_slots": np.full(9, -7, np.int32)}
+    dev = {"xyz": torch.full((4, 3), 7.0, dtype=torch.float32, device="cuda"),
+           "cam_offsets": torch.full((5,), -7, dtype=torch.int64, device="cuda"),
+           "cam_slots": torch.full((9,), -7, dtype=torch.int32, device="cuda")}
+    for what, out in (("host", host), ("device", dev)):
+        got = eng.extract_points_voxel_cameras(refs, rows, 0.02, out=out, **kw)
+        assert got["plain_total"] == 0 and got["cam_total"] == 0 and not np.asarray(got["offsets"]).any(), what
+        co = out["cam_offsets"].cpu().numpy() if what == "device" else out["cam_offsets"]
+        cs = out["cam_slots"].cpu().numpy() if what == "device" else out["cam_slots"]
+        xyz = out["xyz"].cpu().numpy() if what == "device" else out["xyz"]
+        assert co[0] == 0 and (co[1:] == -7).all() and (cs == -7).all() and (xyz == 7.0).all(), what
+
+
 def test_binding_retries_once(pkg, engines, monkeypatch):
     """a cam_slots sized by the binding that turns out too small: the call is repeated once with the reported total"""
     g, eng = engines("plane_64x48_n7")
