@@ -1460,7 +1460,12 @@ int sdm_get_timing(sdm_ctx *ctx, double ms_total[SDM_NUM_STAGES], long long laun
  *          each compared with the plain-division chain's cell, validity and offset;
  * which 10: K1's fast_atan2_deg_x1 (PM.cc:414) vs fast_atan2_deg(y, 1) over all 2^32 float inputs; out[1] = an
  *          order-independent 64-bit digest of its results, equal to OpenCV 2.4.5's cvFastArctan(y, 1)
- *          (tests/golden/fastatan2_x1_digest.json). */
+ *          (tests/golden/fastatan2_x1_digest.json);
+ * which 11: the reciprocal-form quotient vs the IEEE division over the operand ranges K1's per-pair boxes prove (range,
+ *          sigma and Eq. 8 quotients, PM.cc:896-897, 457, 845-875): divisors in [2^-30, 2^30], numerators +0 or in
+ *          [2^-66, 2^40], both signs, all-ones significands; out[1] = 2^32 pairs;
+ * which 12: no arithmetic -- out[0] = pairs of the last compute call whose search-range quotients take the reciprocal
+ *          form, + (pairs whose sigma / Eq. 8 quotients do) << 32; out[1] = pairs of that call. */
 int sdm_selftest(sdm_ctx *ctx, int which, unsigned long long out[2]);
 /* name of the device the context runs on, e.g. "gfx950" */
 const char *sdm_device_arch(sdm_ctx *ctx);

@@ -45,6 +45,9 @@ struct alignas(16) PairConst {  // per (reference, neighbour): hoisted out of th
                                 // bit 1: line_quot_safe(F) -- the line's quotients need no per-lane guard
                                 // bit 2: the search range at the principal point spans at least MASK_HINT_L columns (or cannot be
                                 // told): K1's waves then ask themselves whether the mask scan pays (scan_masked)
+                                // bit 3: the search range's quotients stay inside the operand boxes of quot_boxes
+                                // bit 4: so do ustar_var and Eq. 8 for every lane whose denom (PM.cc:455) lies in
+                                // [2^E, 2^30); bits 8-15: E, as a biased float exponent
     // -- the rest (K4, set-up) --
     float Ry[3];                // R21 row 1
     float ty;
@@ -430,8 +433,13 @@ __device__ __forceinline__ float fast_atan2_deg_x1(float y)
 // bit 16 sqrtf(ustar_var) (PM.cc:818) as v_rsq_f32 + one FMA residual step, exact for every x in [2^-100, 2^127)
 //        (tools/ubench/exact_ops.hip walks all positive floats; sdm_selftest(6) repeats it)
 // bit 17 the refinement's two records as one 16-byte gather each
+// bits 18-20 the search's remaining float quotients in reciprocal form (rcp_fast + quot_fast) for pairs whose operands
+//        k_pair_setup could bound over the whole image (quot_boxes; PairConst::clean bits 3, 4), one bit per group:
+//        bit 18 the search range's fx*x_min / z_min and fx*x_max / z_max (PM.cc:896-897) -- wave-uniform, no per-lane test
+//        bit 19 ustar_var = 2*istd^2 / denom (PM.cc:457) with its square root; bit 20 Eq. 8 at ustar, ustar - s, ustar + s
+//        (PM.cc:845-875): both under ONE per-lane window test on denom, which takes the place of sqrt_exact's own
 #ifndef SDM_K1_OPT
-#define SDM_K1_OPT 0x3a27f
+#define SDM_K1_OPT 0x1fa27f
 #endif
 
 // what one search reads of its PairConst, as float indices into the block `cv` points at: the PairConst itself
@@ -501,6 +509,8 @@ __device__ __forceinline__ float rec_lerp_grad_w(const float4& r, float y0w)
 // (fminf/fmaxf cost a canonicalising v_max each), and the clamps of PM.cc:906-909 moved behind the float->int
 // conversion: ceil/floor and a clamp to integer bounds commute, and v_cvt_i32_f32 saturates (+-Inf ends clamp like
 // the float statement).  hi comes back clamped to W-1 (the scan never visits column W, N3).
+__device__ __forceinline__ float rcp_fast(float b);  // (reciprocal-form quotients, below)
+__device__ __forceinline__ float quot_fast(float a, float b, float r);
 __device__ __forceinline__ int cvt_i32_sat(float x)
 {
     int r;
@@ -508,12 +518,23 @@ __device__ __forceinline__ int cvt_i32_sat(float x)
     return r;
 }
 __device__ __forceinline__ bool search_range_int1(float fx, float cx, float rxxp, float rzxp, float tx, float tz,
-                                                  float mind, float maxd, int W, int& lo, int& hi)
+                                                  float mind, float maxd, int W, int& lo, int& hi, bool boxed = false)
 {
     float x_min = rxxp * mind + tx, z_min = rzxp * mind + tz;
     float x_max = rxxp * maxd + tx, z_max = rzxp * maxd + tz;
+#if SDM_K1_OPT & 0x40000
+    float u1, u2;
+    if (boxed) {  // wave-uniform: PairConst::clean bit 3, both quotients inside quot_boxes' operand ranges
+        u1 = quot_fast(fx * x_min, z_min, rcp_fast(z_min)) + cx;
+        u2 = quot_fast(fx * x_max, z_max, rcp_fast(z_max)) + cx;
+    } else {
+        u1 = fx * x_min / z_min + cx;
+        u2 = fx * x_max / z_max + cx;
+    }
+#else
     const float u1 = fx * x_min / z_min + cx;
     const float u2 = fx * x_max / z_max + cx;
+#endif
     const float mn = __builtin_amdgcn_fmed3f(u1, u2, -__builtin_inff());
     const float mx = __builtin_amdgcn_fmed3f(u1, u2, __builtin_inff());
     lo = min(max(cvt_i32_sat(ceilf(mn)), 0), W);
@@ -622,6 +643,131 @@ __device__ __forceinline__ bool line_quot_safe(const float* F)
         ok = ok && (u == 0u || (mag >= ((127u - 36u) << 23) && mag <= ((127u + 20u) << 23)));
     }
     return ok;
+}
+
+// ---- the search's other float quotients without a per-operand guard (SDM_K1_OPT bits 18-20) -------------------------------
+// quot_fast(a, b, rcp_fast(b)) is the IEEE quotient a / b bit for bit whenever
+//     (D)  2^-30 <= |b| <= 2^30                   (QB_DIV_*)
+//     (N)  a is +0, or 2^-66 <= |a| <= 2^40       (QB_NUM_*)
+// r = RN(1/b) (rcp_fast is correctly rounded for every divisor, sdm_selftest(6)) lies in [2^-30, 2^30]; a non-zero quotient in
+// [2^-97, 2^71]: normal.  A residual fma(-q, b, a) is exact -- Markstein's premise -- when a - q*b, a multiple of
+// ulp(q) ulp(b) >= 2^-48 |a| >= 2^-114, is representable: it is, and it is normal ("above the denormal range"), so two
+// Markstein steps from q0 = a*r deliver RN(a/b).  a = +0 gives a zero with the divisor's sign under both statements
+// (q0 = +-0, e = +0, every later sum adds equal-signed zeros); a = -0 would NOT (the residual +0 turns the zero positive),
+// which is why (N) says +0.  sdm_selftest(11) sweeps exactly (D) x (N): all-ones significands, both signs, zero numerators.
+//
+// quot_boxes decides ONCE PER PAIR, in k_pair_setup, whether every operand the searches of that pair can meet obeys (D) and
+// (N).  It evaluates the statements epipolar_search executes in interval arithmetic over the whole reference image
+// (x in [0, W-1], y in [0, H-1]); every interval operation is rounded outward by 2^-20 relative (16 times the float rounding
+// of the statement plus that of the bound's own evaluation) and 2^-100 absolute (an underflowing product).  A pair that
+// cannot be bounded is refused and keeps the divisions: nothing is claimed about degenerate geometry.
+//
+// Inputs: every entry of R21 rows 0 and 2, t21.x, t21.z, cx, cy is +0 or of magnitude in [2^-36, 2^20] (the window
+// line_quot_safe asks of F12); fx, fy, min_depth, max_depth are POSITIVE and in that window; t21.x is not zero.
+// Non-zero numerators ("zero or not small" replaces a grid argument: it needs no lower bound on the rotation's entries).
+// LEMMA: s = RN(u + v) for floats u, v is zero or |s| >= 2^-25 max(|u|, |v|).  (Say |u| >= |v|.  If |v| <= |u|/2 the
+// exact sum is at least |u|/2.  Otherwise both ulps are at least ulp(u)/2 > 2^-25 |u|, the exact sum is a multiple of the
+// smaller one, and rounding keeps a multiple.)  A sum that cancels is +0.
+//   range (bit 18, PairConst::clean bit 3):  x_min = RN(RN(rxxp*mind) + tx) with tx != 0 is +0 or >= 2^-25 |tx| in magnitude;
+//     the numerator RN(fx * x_min) is +0 (fx > 0) or >= fx * 2^-25 |tx| (1 - 2^-24), which quot_boxes requires to be
+//     >= 2^-66.  The divisors z_min, z_max and the numerators' upper ends come from the boxes.  No per-lane condition.
+//   Eq. 8 and sigma (bits 19, 20; clean bit 4) hold for the lanes whose denom (PM.cc:455) lies in [2^E, 2^30), E per pair
+//     in clean bits 8-15 (biased) -- the ONE per-lane test, in the place of sqrt_exact's:
+//     * sigma: the numerator RN(RN(2*istd)*istd) is wave-uniform, checked against (N) per pair; the quotient lies in
+//       [2^-96, 2^70], inside sqrt_exact's window, whose own test is dropped.
+//     * ustar: best_pixel in [1, W-2] (PM.cc:449-450) plus C = (g*pe + q*ge/theta) / denom in double.  Cauchy-Schwarz:
+//       |g*pe + q*ge/theta| <= sqrt(g^2 + q^2/theta) sqrt(pe^2 + ge^2/theta); the first root is sqrt(denom) up to 2^-22, the
+//       second the matching cost of a candidate that was taken, below 10^6 (1 + 2^-18) (PM.cc:437; the approximate arg-min
+//       is within COST_BAND float steps).  With every rounding of the statement: |C| <= 1002 / sqrt(denom).
+//       s = sqrt(ustar_var) <= 1.4143 istd / sqrt(denom).  E is the smallest exponent with (1002 + 1.4143 istd) / 2^(E/2) <= 4 W,
+//       so u = ustar, ustar -+ s all lie in [1 - 4W, W - 2 + 4W], inside the box [-4W, 5W] the intervals are evaluated for.
+//       (A NaN, Inf or negative denom is outside the window: the test is an unsigned comparison of its bits.)
+//     * numerator N = RN(num1 - num2), num1 = RN(rzxp*ucx), num2 = RN(fx*rxxp); required: R21(0,2) != 0, cx != 0, rzxp > 0
+//       over the image.  rxxp = RN(RN(p0 + p1) + R21(0,2)) is +0 or >= 2^-25 |R21(0,2)|.  If num2 != 0 the lemma gives
+//       |N| >= 2^-25 |num2| >= 2^-50 fx |R21(0,2)| (1 - 2^-24) or N = +0.  If num2 = +0: N = num1, and ucx = RN(u - cx) is +0 or
+//       >= 2^-25 |cx|, so N is +0 or >= min(rzxp) 2^-25 |cx| (1 - 2^-24).  Neither product underflows, ucx is never -0, so
+//       N is never -0.  quot_boxes requires the smaller of the two bounds to be >= 2^-66.
+constexpr float QB_DIV_LO = 0x1p-30f, QB_DIV_HI = 0x1p30f, QB_NUM_LO = 0x1p-66f, QB_NUM_HI = 0x1p40f;
+constexpr unsigned QB_DWIN_END = 157u << 23;  // bits(2^30): the per-lane window on denom ends here
+constexpr float QB_U_SPAN = 4.0f;             // the Eq. 8 boxes cover u in [-QB_U_SPAN W, (QB_U_SPAN + 1) W]
+struct Box {
+    float lo, hi;
+};
+__device__ inline Box box_out(float lo, float hi)
+{
+    return Box{lo - fabsf(lo) * 0x1p-20f - 0x1p-100f, hi + fabsf(hi) * 0x1p-20f + 0x1p-100f};
+}
+__device__ inline Box box_pt(float v) { return Box{v, v}; }
+__device__ inline Box box_neg(const Box& a) { return Box{-a.hi, -a.lo}; }
+__device__ inline Box box_add(const Box& a, const Box& b) { return box_out(a.lo + b.lo, a.hi + b.hi); }
+__device__ inline Box box_mul(const Box& a, const Box& b)  // (finite operands: the callers check their inputs first)
+{
+    const float p0 = a.lo * b.lo, p1 = a.lo * b.hi, p2 = a.hi * b.lo, p3 = a.hi * b.hi;
+    return box_out(fminf(fminf(p0, p1), fminf(p2, p3)), fmaxf(fmaxf(p0, p1), fmaxf(p2, p3)));
+}
+__device__ inline float box_mag_hi(const Box& a) { return fmaxf(fabsf(a.lo), fabsf(a.hi)); }
+__device__ inline bool box_divisor_ok(const Box& a)  // (D): excludes zero, magnitudes in [2^-30, 2^30]
+{
+    return (a.lo > 0.0f || a.hi < 0.0f) && fminf(fabsf(a.lo), fabsf(a.hi)) >= QB_DIV_LO && box_mag_hi(a) <= QB_DIV_HI;
+}
+__device__ inline bool quot_input_ok(float v)  // +0, or a magnitude in [2^-36, 2^20]
+{
+    const unsigned u = __float_as_uint(v), mag = u & 0x7FFFFFFFu;
+    return u == 0u || (mag >= ((127u - 36u) << 23) && mag <= ((127u + 20u) << 23));
+}
+// pixel_depth (Eq. 8) for a lane inside the pair's operand boxes
+__device__ __forceinline__ float pixel_depth_boxed(float uj, float fx, float cx, float rzxp, float rxxp, float tx, float tz)
+{
+    float ucx = uj - cx;
+    float num1 = rzxp * ucx;
+    float num2 = fx * rxxp;
+    float denom1 = -tz * ucx;
+    float denom2 = fx * tx;
+    const float den = denom1 + denom2;
+    return quot_fast(num1 - num2, den, rcp_fast(den));
+}
+// returns the bits of PairConst::clean it decides: 8 (range), 16 | E << 8 (sigma and Eq. 8 inside the denom window)
+__device__ inline int quot_boxes(const float* Rx, const float* Rz, float tx, float tz, float istd, float fx, float fy, float cx,
+                                 float cy, float mind, float maxd, int W, int H)
+{
+    bool in = quot_input_ok(tx) && quot_input_ok(tz) && quot_input_ok(cx) && quot_input_ok(cy) && quot_input_ok(fx) &&
+              quot_input_ok(fy) && quot_input_ok(mind) && quot_input_ok(maxd);
+    for (int i = 0; i < 3; i++) in = in && quot_input_ok(Rx[i]) && quot_input_ok(Rz[i]);
+    in = in && fx > 0.0f && fy > 0.0f && mind > 0.0f && maxd > 0.0f && tx != 0.0f && W >= 2 && H >= 2 && W <= 65536 && H <= 65536;
+    if (!in) return 0;
+    // xp0 = ((float)x - cx) / fx, xp1 = ((float)y - cy) / fy (PM.cc:862): monotone in x, y for positive focal lengths
+    const Box xp0 = box_out((0.0f - cx) / fx, ((float)(W - 1) - cx) / fx);
+    const Box xp1 = box_out((0.0f - cy) / fy, ((float)(H - 1) - cy) / fy);
+    // row_dot_xp: (r0*xp0 + r1*xp1) + r2*1
+    const Box rxxp = box_add(box_add(box_mul(box_pt(Rx[0]), xp0), box_mul(box_pt(Rx[1]), xp1)), box_pt(Rx[2]));
+    const Box rzxp = box_add(box_add(box_mul(box_pt(Rz[0]), xp0), box_mul(box_pt(Rz[1]), xp1)), box_pt(Rz[2]));
+    int bits = 0;
+    {  // search_range_int1: x = rxxp*d + tx, z = rzxp*d + tz, fx*x / z for d = mind, maxd
+        bool ok = fx * 0x1p-25f * fabsf(tx) * (1.0f - 0x1p-20f) >= QB_NUM_LO;
+        const float ds[2] = {mind, maxd};
+        for (int k = 0; k < 2; k++) {
+            const Box xk = box_add(box_mul(rxxp, box_pt(ds[k])), box_pt(tx));
+            const Box zk = box_add(box_mul(rzxp, box_pt(ds[k])), box_pt(tz));
+            ok = ok && box_divisor_ok(zk) && box_mag_hi(box_mul(box_pt(fx), xk)) <= QB_NUM_HI;
+        }
+        if (ok) bits |= 8;
+    }
+    {  // ustar_var and pixel_depth for u in [-4W, 5W]
+        const float w = (float)W;
+        const Box ucx = box_add(Box{-QB_U_SPAN * w, (QB_U_SPAN + 1.0f) * w}, box_pt(-cx));
+        const Box num = box_add(box_mul(rzxp, ucx), box_neg(box_mul(box_pt(fx), rxxp)));
+        const Box den = box_add(box_mul(box_pt(-tz), ucx), box_mul(box_pt(fx), box_pt(tx)));
+        const float nvar = 2 * istd * istd;  // the statement's numerator (PM.cc:457)
+        const float lb = fminf(0x1p-50f * fx * fabsf(Rx[2]), rzxp.lo * 0x1p-25f * fabsf(cx)) * (1.0f - 0x1p-20f);
+        bool ok = box_divisor_ok(den) && box_mag_hi(num) <= QB_NUM_HI && Rx[2] != 0.0f && cx != 0.0f && rzxp.lo >= 0x1p-10f &&
+                  lb >= QB_NUM_LO && quot_input_ok(istd) && istd > 0.0f && nvar >= QB_NUM_LO && nvar <= QB_NUM_HI;
+        // E: the first power of two above ((1002 + 1.4143 istd) / (4 W))^2, at least 2^-30
+        const float root = (1002.0f + 1.4143f * istd) / (QB_U_SPAN * w) * (1.0f + 0x1p-10f);
+        const unsigned eb = max((__float_as_uint(root * root) >> 23) + 1u, 97u);
+        ok = ok && eb < (QB_DWIN_END >> 23);
+        if (ok) bits |= 16 | (int)(eb << 8);
+    }
+    return bits;
 }
 
 struct ScanState {
@@ -1038,7 +1184,7 @@ __device__ __forceinline__ bool epipolar_search(const float4* __restrict__ nrec,
     float tx = cv[CV_TX], tz = cv[CV_TZ];
     int lo, hi;
 #if SDM_K1_OPT & 0x20
-    live &= search_range_int1(fx, cx, rxxp, rzxp, tx, tz, mind, maxd, W, lo, hi);  // PM.cc:404; N5
+    live &= search_range_int1(fx, cx, rxxp, rzxp, tx, tz, mind, maxd, W, lo, hi, (clean & 8) != 0);  // PM.cc:404; N5
 #else
     live &= search_range_int(fx, cx, rxxp, rzxp, tx, tz, mind, maxd, W, lo, hi);  // PM.cc:404; N5
     if (hi > W - 1) hi = W - 1;
@@ -1171,15 +1317,49 @@ __device__ __forceinline__ bool epipolar_search(const float4* __restrict__ nrec,
     float gpe = g * best_pe;
     float ustar = (float)((double)best_pixel +
                           ((double)gpe + inv_theta * (double)q * (double)best_ge) / (double)denom);
-    float ustar_var = 2 * cv[CV_ISTD] * cv[CV_ISTD] / denom;  // PM.cc:457
     best_u = ustar;
     best_v = -(ab * ustar + cb);  // PM.cc:460
+#if SDM_K1_OPT & 0x180000
+    // clean bit 4 (wave-uniform) and denom inside the pair's window [2^E, 2^30) (per lane; the one test, where sqrt_exact's
+    // was): ustar_var, its root and the three Eq. 8 quotients meet only operands quot_boxes has bounded
+    float d0, dmin, dmax;
+    const unsigned dwin_lo = ((unsigned)clean & 0xFF00u) << 15;
+    if ((clean & 16) && (__float_as_uint(denom) - dwin_lo) < (QB_DWIN_END - dwin_lo)) {
+        const float nvar = 2 * cv[CV_ISTD] * cv[CV_ISTD];
+#if SDM_K1_OPT & 0x80000
+        const float ustar_var = quot_fast(nvar, denom, rcp_fast(denom));  // PM.cc:457
+        const float rs = __builtin_amdgcn_rsqf(ustar_var);                // sqrt_exact, inside its window by construction
+        const float y0 = ustar_var * rs, hs = 0.5f * rs;
+        const float s = __builtin_fmaf(__builtin_fmaf(-y0, y0, ustar_var), hs, y0);
+#else
+        const float s = sqrt_exact(nvar / denom);
+#endif
+#if SDM_K1_OPT & 0x100000
+        d0 = pixel_depth_boxed(ustar, fx, cx, rzxp, rxxp, tx, tz);
+        dmin = pixel_depth_boxed(ustar - s, fx, cx, rzxp, rxxp, tx, tz);
+        dmax = pixel_depth_boxed(ustar + s, fx, cx, rzxp, rxxp, tx, tz);
+#else
+        d0 = pixel_depth(ustar, fx, cx, rzxp, rxxp, tx, tz);
+        dmin = pixel_depth(ustar - s, fx, cx, rzxp, rxxp, tx, tz);
+        dmax = pixel_depth(ustar + s, fx, cx, rzxp, rxxp, tx, tz);
+#endif
+    } else {
+        const float ustar_var = 2 * cv[CV_ISTD] * cv[CV_ISTD] / denom;  // PM.cc:457
+        // ComputeInvDepthHypothesis PM.cc:806-829
+        d0 = pixel_depth(ustar, fx, cx, rzxp, rxxp, tx, tz);
+        const float s = sqrt_exact(ustar_var);
+        dmin = pixel_depth(ustar - s, fx, cx, rzxp, rxxp, tx, tz);
+        dmax = pixel_depth(ustar + s, fx, cx, rzxp, rxxp, tx, tz);
+    }
+#else
+    float ustar_var = 2 * cv[CV_ISTD] * cv[CV_ISTD] / denom;  // PM.cc:457
 
     // ComputeInvDepthHypothesis PM.cc:806-829
     float d0 = pixel_depth(ustar, fx, cx, rzxp, rxxp, tx, tz);
     float s = sqrt_exact(ustar_var);
     float dmin = pixel_depth(ustar - s, fx, cx, rzxp, rxxp, tx, tz);
     float dmax = pixel_depth(ustar + s, fx, cx, rzxp, rxxp, tx, tz);
+#endif
     float e1 = fabsf(dmax - d0), e2 = fabsf(dmin - d0);
     rho_o = d0;
     sigma_o = (e1 < e2) ? e2 : e1;  // cv::max(a,b) = (a<b)?b:a

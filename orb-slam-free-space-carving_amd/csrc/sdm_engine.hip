@@ -2793,6 +2793,14 @@ int sdm_selftest(sdm_ctx* c, int which, unsigned long long out[2])
         hipLaunchKernelGGL(k_selftest_atan_x1, dim3(4096), dim3(BLOCK), 0, c->stream, c->d_stats + 5, c->d_stats + 6);
     } else if (which == 3) {
         hipLaunchKernelGGL(k_selftest_gates, dim3(4096), dim3(BLOCK), 0, c->stream, c->dprm, c->d_stats + 5, c->d_stats + 6);
+    } else if (which == 11) {  // 2^32 operand pairs
+        hipLaunchKernelGGL(k_selftest_quot_boxes, dim3(4096), dim3(BLOCK), 0, c->stream, 4096, c->d_stats + 5, c->d_stats + 6);
+    } else if (which == 12) {  // the pair constants of the last compute call
+        const sdm_ctx::TableKey& key = c->sets[c->cur_set].key;
+        if (!key.valid || !key.has_consts || !c->d_pairs) return fail(SDM_EINVAL, "no pair constants staged");
+        const int np = key.n_ref * key.n;
+        hipLaunchKernelGGL(k_selftest_pair_bits, dim3((np + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d_pairs, np,
+                           c->d_stats + 5, c->d_stats + 6);
     } else {
         return fail(SDM_EINVAL, "unknown selftest");
     }

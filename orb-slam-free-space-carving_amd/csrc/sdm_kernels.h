@@ -207,6 +207,11 @@ __global__ void k_pair_setup(const KfMeta* __restrict__ meta, const int* __restr
         search_range(m1.fx, m1.cx, pc.Rx[2], pc.Rz[2], pc.tx, pc.tz, mind ? mind[r] : 0.f, maxd ? maxd[r] : 0.f, W, umin, umax);
         if (!(umax - umin < (float)MASK_HINT_L)) pc.clean |= 4;  // (NaN ends: cannot tell)
     }
+#if SDM_K1_OPT & 0x1c0000
+    // bits 3, 4, 8-15: the pair's operand boxes admit the reciprocal-form quotients (a call without depth priors: refused)
+    pc.clean |= quot_boxes(pc.Rx, pc.Rz, pc.tx, pc.tz, pc.istd, m1.fx, m1.fy, m1.cx, m1.cy, mind ? mind[r] : 0.f, maxd ? maxd[r] : 0.f,
+                           W, H);
+#endif
     // K4's approximate projection (k4_proj_bounds): the largest |xp0|, |xp1| any pixel of the reference image can have
     {
         const float s = 1.0f + 0x1p-20f;
@@ -2124,6 +2129,64 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_quot(int iters, unsigned lon
         if (cnt) atomicAdd(bad, cnt);
         atomicAdd(tested, n);
     }
+}
+
+// which = 11: quot_fast vs the IEEE division over the operand boxes quot_boxes proves (sdm_device.h, SDM_K1_OPT bits 18-20):
+// divisors of magnitude in [2^-30, 2^30], numerators +0 or of magnitude in [2^-66, 2^40], every significand, both signs;
+// one draw in 8 forces a special case -- a zero numerator, all-ones significands, the boxes' corner values, a numerator
+// next to a multiple of the divisor (quotients next to a rounding boundary).  4096 x BLOCK x iters pairs; bits compared.
+__global__ __launch_bounds__(BLOCK) void k_selftest_quot_boxes(int iters, unsigned long long* __restrict__ bad,
+                                                               unsigned long long* __restrict__ tested)
+{
+    unsigned s = 0x27D4EB2Fu * (blockIdx.x * BLOCK + threadIdx.x + 1);
+    unsigned long long cnt = 0, n = 0;
+    for (int i = 0; i < iters; i++) {
+        const unsigned ba = xs32(s), bb = xs32(s), pick = xs32(s);
+        float a = __uint_as_float((ba & 0x807FFFFFu) | ((61u + (ba >> 23) % 106u) << 23));  // 2^-66 .. just below 2^40
+        float b = __uint_as_float((bb & 0x807FFFFFu) | ((97u + (bb >> 23) % 60u) << 23));   // 2^-30 .. just below 2^30
+        const unsigned sa = ba & 0x80000000u, sb = bb & 0x80000000u;
+        switch (pick & 63u) {
+        case 0: a = 0.0f; break;
+        case 1: a = __uint_as_float(__float_as_uint(a) | 0x7FFFFFu); break;
+        case 2: b = __uint_as_float(__float_as_uint(b) | 0x7FFFFFu); break;
+        case 3: a = __uint_as_float(__float_as_uint(a) | 0x7FFFFFu); b = __uint_as_float(__float_as_uint(b) | 0x7FFFFFu); break;
+        case 4: a = __uint_as_float(sa | __float_as_uint(QB_NUM_HI)); break;
+        case 5: a = __uint_as_float(sa | (__float_as_uint(QB_NUM_LO) + ((pick >> 8) & 1u))); break;
+        case 6: b = __uint_as_float(sb | __float_as_uint(QB_DIV_HI)); break;
+        case 7: b = __uint_as_float(sb | (__float_as_uint(QB_DIV_LO) + ((pick >> 8) & 1u))); break;
+        case 8: {  // a next to k * b for a small odd or even k (inside the numerator range for every b of the box)
+            const float k = (float)(1u + ((pick >> 8) & 255u));
+            a = __uint_as_float(__float_as_uint(k * b) + ((pick >> 16) & 3u) - 1u);
+            break;
+        }
+        default: break;
+        }
+        const float q = quot_fast(a, b, rcp_fast(b)), e = a / b;
+        if (__float_as_uint(q) != __float_as_uint(e)) cnt++;
+        n++;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_down(cnt, o);
+        n += __shfl_down(n, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (cnt) atomicAdd(bad, cnt);
+        atomicAdd(tested, n);
+    }
+}
+
+// which = 12: how many pairs of the current table set carry PairConst::clean bit 3 / bit 4 (the pairs whose searches take the
+// reciprocal-form quotients): bad <- pairs with bit 3 | pairs with bit 4 << 32, tested <- pairs
+__global__ __launch_bounds__(BLOCK) void k_selftest_pair_bits(const PairConst* __restrict__ pairs, int n_pairs,
+                                                              unsigned long long* __restrict__ bad,
+                                                              unsigned long long* __restrict__ tested)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_pairs) return;
+    const int cl = pairs[i].clean;
+    const unsigned long long v = ((cl & 8) ? 1ull : 0ull) | ((cl & 16) ? (1ull << 32) : 0ull);
+    if (v) atomicAdd(bad, v);
+    atomicAdd(tested, 1ull);
 }
 
 // which = 3: closed-form angle gates vs the reference statement, for d = theta2 - ref over
