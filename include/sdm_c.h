@@ -1465,7 +1465,11 @@ int sdm_get_timing(sdm_ctx *ctx, double ms_total[SDM_NUM_STAGES], long long laun
  *          sigma and Eq. 8 quotients, PM.cc:896-897, 457, 845-875): divisors in [2^-30, 2^30], numerators +0 or in
  *          [2^-66, 2^40], both signs, all-ones significands; out[1] = 2^32 pairs;
  * which 12: no arithmetic -- out[0] = pairs of the last compute call whose search-range quotients take the reciprocal
- *          form, + (pairs whose sigma / Eq. 8 quotients do) << 32; out[1] = pairs of that call. */
+ *          form, + (pairs whose sigma / Eq. 8 quotients do) << 32; out[1] = pairs of that call;
+ * which 13, 14, 15: K1's decided f64 roundings vs the statements as written -- 13 ustar (PM.cc:458), 14 GetFusion's two
+ *          sums over chains of 1..20 terms (PM.cc:936-937), 15 GetFusion's pjsj / rsj and sqrtf(1 / rsj) (PM.cc:225-226);
+ *          out[1] = draws inside the operand window that were handed to the statement (undecided), out of
+ *          2^27 (13), 330301440 (14) and 2^28 (15) such draws; draws outside the windows and special operands on top. */
 int sdm_selftest(sdm_ctx *ctx, int which, unsigned long long out[2]);
 /* name of the device the context runs on, e.g. "gfx950" */
 const char *sdm_device_arch(sdm_ctx *ctx);

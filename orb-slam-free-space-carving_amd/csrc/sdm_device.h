@@ -438,8 +438,15 @@ __device__ __forceinline__ float fast_atan2_deg_x1(float y)
 //        bit 18 the search range's fx*x_min / z_min and fx*x_max / z_max (PM.cc:896-897) -- wave-uniform, no per-lane test
 //        bit 19 ustar_var = 2*istd^2 / denom (PM.cc:457) with its square root; bit 20 Eq. 8 at ustar, ustar - s, ustar + s
 //        (PM.cc:845-875): both under ONE per-lane window test on denom, which takes the place of sqrt_exact's own
+// bits 21, 22 f64 quotients that only feed RN32(RN64(c + quotient)) are DECIDED, not divided (decided_sum, below):
+//        bit 21 ustar's N / denom (PM.cc:458) inside bit 19/20's denom window, seeded by the rcp_fast(denom) ustar_var needs
+//        bit 22 GetFusion's two sums in K1 and k_fuse_open (fusion_accum_decided): one Newton step from v_rcp_f32(sigma^2)
+// bit 23 (off: within run-to-run noise, EXPERIMENTS.md) GetFusion's pjsj / rsj and sqrtf(1 / rsj) in reciprocal form under a
+//        per-lane operand window (fusion_tail): exact, 39 -> 15 instructions, but once per workgroup
+// bit 24 scan_batch issues its four gathers in slot order and pins each record just before its slot is looked at: slot 0 runs
+//        behind s_waitcnt vmcnt(3), slot k behind vmcnt(3-k), instead of every slot behind all four gathers
 #ifndef SDM_K1_OPT
-#define SDM_K1_OPT 0x1fa27f
+#define SDM_K1_OPT 0x17fa27f
 #endif
 
 // what one search reads of its PairConst, as float indices into the block `cv` points at: the PairConst itself
@@ -622,6 +629,57 @@ __device__ __forceinline__ float sqrt_exact(float x)
     return sqrtf(x);
 #endif
 }
+
+// ---- f64 quotients that only feed a rounding (SDM_K1_OPT bits 21, 22) ------------------------------------------------------
+// The reference's float/double promotion leaves statements of the shape  x = (float)((double)c + N / d)  on K1's path: the
+// refinement's ustar (PM.cc:458) and GetFusion's two running sums (PM.cc:936-937).  The IEEE f64 quotient T = RN64(N / d)
+// feeds nothing but f(T), f(t) = RN32(RN64(c + t)), and f is non-decreasing in t over the extended reals.  So the quotient
+// need not be correctly rounded, only DECIDED:
+//   LEMMA.  Let Q be a double with |T - Q| <= delta |Q|, delta = 2^-40.  1 - delta and 1 + delta are doubles, an FMA forms
+//   its product exactly, so lo = (float)fma(Q, 1 - delta, c) IS f(Q (1 - delta)) and hi = (float)fma(Q, 1 + delta, c) IS
+//   f(Q (1 + delta)).  T lies between the two arguments (in either order: Q < 0 flips them, and the equality test below is
+//   symmetric), hence lo == hi implies f(T) = lo.  Q = +-0 means T = +-0 with the same sign (below), both sides are f(+-0).
+//   A NaN never compares equal.  lo == hi == +-Inf: then f(T) is that infinity as well by monotonicity, as long as Q itself
+//   is not an overflowed product -- the float range ends 2^896 below the double range, so a finite T within 2^-40 of a
+//   finite Q and c + Q (1 -+ delta) both beyond the float range put c + T beyond it too; if N * y overflows, |T| >= 2^1023
+//   and f(T) is the same infinity (c is a float).
+// Lanes with lo != hi (an argument within 2^-40 relative of a float rounding boundary of the sum: about 8 in 10^6) run the
+// reference statement as written.
+//   Q = N * y with y ~ 1/d from ONE Newton step in double on a float seed y0:  e = fma(-d, y0, 1), y = fma(e, y0, y0).
+//   PREMISE: d is a positive normal double in [2^-200, 2^200] and |1 - d y0| <= 2^-21.  Then d y = (1 - e')(1 + e') up to
+//   two roundings of 2^-53, |d y - 1| <= 2^-42 + 2^-51, |Q / (N/d) - 1| <= 2^-41.9 + 2^-53, and with T's own rounding
+//   |T - Q| < 2^-41 |Q| -- unless Q or T is denormal.  GetFusion: N is 1 or a float (zero, or |rho| >= 2^-149) and
+//   y >= 2^-101: never.  ustar: then |N| < 2^-800, |T| and |Q (1 +- delta)| are below 2^-750, and c >= 1 (best_pixel >= 1,
+//   PM.cc:449-450) absorbs either one: lo = hi = f(T) = c.  A zero N gives Q = T = N's zero (y > 0, d > 0); an infinite N
+//   gives Q = T = that infinity.
+// The premise is PROVED from an operand window each path tests, not assumed (no certificate on y is computed):
+//   ustar:     d = denom inside the pair's window [2^E, 2^30), E >= -30 (quot_boxes; the test that guards ustar_var), and
+//              y0 = rcp_fast(denom) = RN32(1 / denom) (sdm_selftest(6)): |1 - d y0| <= 2^-24.
+//   GetFusion: sigma's bits in [bits(2^-50), bits(2^50)) -- positive, normal: ONE unsigned compare -- so d = s2 =
+//              (double)sigma^2 (exact) in [2^-100, 2^100), the seed's operand RN32(sigma * sigma) is normal and within 2^-24
+//              of s2, and y0 = v_rcp_f32 of it (1 ulp, 2^-23): |1 - d y0| <= 1.5 * 2^-23 + 2^-46 < 2^-22.  (The bound the
+//              lemma needs, 2^-21, leaves room for a seed of 2.8 ulp.)
+// sdm_selftest(13) / (14) compare both forms with the plain statements over exactly these windows and outside them.
+constexpr double DECIDE_LO = 1.0 - 0x1p-40, DECIDE_HI = 1.0 + 0x1p-40;
+__device__ __forceinline__ bool decided_sum(double c, double Q, float& out)
+{
+    const float lo = (float)__builtin_fma(Q, DECIDE_LO, c), hi = (float)__builtin_fma(Q, DECIDE_HI, c);
+    out = lo;
+    return lo == hi;
+}
+__device__ __forceinline__ double rcp_newton_f64(double d, float y0f)
+{
+    const double y0 = (double)y0f;
+    const double e = __builtin_fma(-d, y0, 1.0);
+    return __builtin_fma(e, y0, y0);
+}
+// PM.cc:458 with c = (double)best_pixel, N = (double)(g*pe) + q*ge/theta: as written, and decided (r = rcp_fast(denom))
+__device__ __forceinline__ float ustar_ref(double c, double N, float denom) { return (float)(c + N / (double)denom); }
+__device__ __forceinline__ bool ustar_decided(double c, double N, float denom, float r, float& ustar)
+{
+    return decided_sum(c, N * rcp_newton_f64((double)denom, r), ustar);
+}
+#define USTAR_DECIDED (((SDM_K1_OPT) & 0x200000) && ((SDM_K1_OPT) & 0x180000))
 
 // ---- the epipolar line's quotients without a per-lane guard (SDM_K1_OPT bit 15) ----------------------------------------------
 // a, b, c = (x*F[0+k] + y*F[3+k]) + F[6+k] with integer pixel coordinates 0 <= x, y < 2^16.  If every entry of F12 is +0 or
@@ -889,14 +947,24 @@ __device__ __forceinline__ void scan_batch(const ScanConst& q, int u0, float u0f
 #else
         rs[k] = *reinterpret_cast<const v4f*>(nb_k + off);
 #endif
+#if SDM_K1_OPT & 0x1000000
+        __builtin_amdgcn_sched_barrier(0);  // gathers issue in slot order (hipcc otherwise issues slot 0's last)
+#endif
     }
     // keep each record one 16-byte gather issued here: without this hipcc splits the first record
-    // into a 4-byte load plus a dependent 12-byte load behind the gradient gate (a second round trip)
+    // into a 4-byte load plus a dependent 12-byte load behind the gradient gate (a second round trip).  Pinned all at once
+    // the four turn into s_waitcnt vmcnt(3), (2), (1), (0) back to back, all before slot 0; bit 24 pins record k where slot k
+    // starts (with the gathers held in slot order above, or hipcc issues slot 0's last and slot 0 waits for all four again)
+#if !(SDM_K1_OPT & 0x1000000)
 #pragma unroll
     for (int k = 0; k < NB; k++)
         asm volatile("" : "+v"(rs[k]));
+#endif
 #pragma unroll
     for (int k = 0; k < NB; k++) {
+#if SDM_K1_OPT & 0x1000000
+        asm volatile("" : "+v"(rs[k]));  // slot k waits for its own record only (vmcnt(NB-1-k)), not for all NB
+#endif
         const int uj = u0 + k;
         if (STATS && uj <= q.hi) st->candidates++;
         const float4 r = make_float4(rs[k].x, rs[k].y, rs[k].z, rs[k].w);
@@ -1315,10 +1383,16 @@ __device__ __forceinline__ bool epipolar_search(const float4* __restrict__ nrec,
     float gg = g * g;
     float denom = (float)((double)gg + inv_theta * (double)q * (double)q);  // PM.cc:455
     float gpe = g * best_pe;
+#if USTAR_DECIDED
+    // PM.cc:458's numerator and addend as written; the quotient is decided inside the denom window below
+    const double un = (double)gpe + inv_theta * (double)q * (double)best_ge, uc = (double)best_pixel;
+    float ustar;
+#else
     float ustar = (float)((double)best_pixel +
                           ((double)gpe + inv_theta * (double)q * (double)best_ge) / (double)denom);
     best_u = ustar;
     best_v = -(ab * ustar + cb);  // PM.cc:460
+#endif
 #if SDM_K1_OPT & 0x180000
     // clean bit 4 (wave-uniform) and denom inside the pair's window [2^E, 2^30) (per lane; the one test, where sqrt_exact's
     // was): ustar_var, its root and the three Eq. 8 quotients meet only operands quot_boxes has bounded
@@ -1326,8 +1400,14 @@ __device__ __forceinline__ bool epipolar_search(const float4* __restrict__ nrec,
     const unsigned dwin_lo = ((unsigned)clean & 0xFF00u) << 15;
     if ((clean & 16) && (__float_as_uint(denom) - dwin_lo) < (QB_DWIN_END - dwin_lo)) {
         const float nvar = 2 * cv[CV_ISTD] * cv[CV_ISTD];
+#if USTAR_DECIDED
+        const float rden = rcp_fast(denom);  // RN(1 / denom): the window is inside [2^-30, 2^30)
+        if (!ustar_decided(uc, un, denom, rden, ustar)) ustar = ustar_ref(uc, un, denom);
+#elif SDM_K1_OPT & 0x80000
+        const float rden = rcp_fast(denom);
+#endif
 #if SDM_K1_OPT & 0x80000
-        const float ustar_var = quot_fast(nvar, denom, rcp_fast(denom));  // PM.cc:457
+        const float ustar_var = quot_fast(nvar, denom, rden);  // PM.cc:457
         const float rs = __builtin_amdgcn_rsqf(ustar_var);                // sqrt_exact, inside its window by construction
         const float y0 = ustar_var * rs, hs = 0.5f * rs;
         const float s = __builtin_fmaf(__builtin_fmaf(-y0, y0, ustar_var), hs, y0);
@@ -1344,6 +1424,9 @@ __device__ __forceinline__ bool epipolar_search(const float4* __restrict__ nrec,
         dmax = pixel_depth(ustar + s, fx, cx, rzxp, rxxp, tx, tz);
 #endif
     } else {
+#if USTAR_DECIDED
+        ustar = ustar_ref(uc, un, denom);
+#endif
         const float ustar_var = 2 * cv[CV_ISTD] * cv[CV_ISTD] / denom;  // PM.cc:457
         // ComputeInvDepthHypothesis PM.cc:806-829
         d0 = pixel_depth(ustar, fx, cx, rzxp, rxxp, tx, tz);
@@ -1359,6 +1442,10 @@ __device__ __forceinline__ bool epipolar_search(const float4* __restrict__ nrec,
     float s = sqrt_exact(ustar_var);
     float dmin = pixel_depth(ustar - s, fx, cx, rzxp, rxxp, tx, tz);
     float dmax = pixel_depth(ustar + s, fx, cx, rzxp, rxxp, tx, tz);
+#endif
+#if USTAR_DECIDED
+    best_u = ustar;
+    best_v = -(ab * ustar + cb);  // PM.cc:460
 #endif
     float e1 = fabsf(dmax - d0), e2 = fabsf(dmin - d0);
     rho_o = d0;
@@ -1425,6 +1512,58 @@ __device__ __forceinline__ void fusion_accum(float rho, float sg, float& pjsj, f
     fusion_terms(rho, sg, t_rho, t_one);
     pjsj = (float)((double)pjsj + t_rho);
     rsj = (float)((double)rsj + t_one);
+}
+// The same term with both sums decided (SDM_K1_OPT bit 22; decided_sum, above): K1's tail and k_fuse_open, which are bound
+// by vector issue.  sigma inside [2^-50, 2^50) -- one unsigned compare; zero, denormal, negative, Inf and NaN sigmas are
+// outside -- proves the premise of the Newton step; a term with either sum undecided, or outside the window, runs
+// fusion_accum as written (one shared region).  rho needs no window: a zero, Inf or NaN rho gives Q = T (or a NaN that
+// compares unequal).  sdm_selftest(14).
+constexpr unsigned FD_SG_LO = 77u << 23, FD_SG_END = 177u << 23;  // bits(2^-50), bits(2^50)
+__device__ __forceinline__ bool fusion_accum_try(float rho, float sg, float& pjsj, float& rsj)
+{
+    if ((__float_as_uint(sg) - FD_SG_LO) >= (FD_SG_END - FD_SG_LO)) return false;
+    const double sd = (double)sg;
+    const double y = rcp_newton_f64(sd * sd, __builtin_amdgcn_rcpf(sg * sg));
+    float np, nr;
+    const bool okp = decided_sum((double)pjsj, (double)rho * y, np);
+    const bool okr = decided_sum((double)rsj, y, nr);
+    if (!(okp & okr)) return false;
+    pjsj = np;
+    rsj = nr;
+    return true;
+}
+__device__ __forceinline__ void fusion_accum_decided(float rho, float sg, float& pjsj, float& rsj)
+{
+#if SDM_K1_OPT & 0x400000
+    if (fusion_accum_try(rho, sg, pjsj, rsj)) return;
+#endif
+    fusion_accum(rho, sg, pjsj, rsj);
+}
+
+// GetFusion's result (PM.cc:225-226 / 968-969): rho = pjsj / rsj, sigma = sqrtf(1 / rsj).  With both operands positive and in
+// [2^-40, 2^41) -- quot_fast's window (quot_window_ok, sdm_selftest(5)); two unsigned compares, so zeros of either sign,
+// negative, denormal, Inf and NaN operands are outside -- r = rcp_fast(rsj) IS 1 / rsj (sdm_selftest(6)), in (2^-41, 2^40]:
+// inside sqrt_exact's window [2^-100, 2^127), whose own test is dropped; quot_fast(pjsj, rsj, r) IS pjsj / rsj.  15
+// instructions against two IEEE division sequences and the 17-instruction sqrtf (SDM_K1_OPT bit 23).  sdm_selftest(15).
+__device__ __forceinline__ float2 fusion_tail_ref(float pjsj, float rsj) { return make_float2(pjsj / rsj, sqrtf(1 / rsj)); }
+__device__ __forceinline__ bool fusion_tail_window(float pjsj, float rsj)
+{
+    return ((__float_as_uint(pjsj) - QUOT_MAG_LO) <= (QUOT_MAG_HI - QUOT_MAG_LO)) &
+           ((__float_as_uint(rsj) - QUOT_MAG_LO) <= (QUOT_MAG_HI - QUOT_MAG_LO));
+}
+__device__ __forceinline__ float2 fusion_tail_fast(float pjsj, float rsj)  // inside fusion_tail_window only
+{
+    const float r = rcp_fast(rsj);
+    const float rs = __builtin_amdgcn_rsqf(r);
+    const float y0 = r * rs, hs = 0.5f * rs;
+    return make_float2(quot_fast(pjsj, rsj, r), __builtin_fmaf(__builtin_fmaf(-y0, y0, r), hs, y0));
+}
+__device__ __forceinline__ float2 fusion_tail(float pjsj, float rsj)
+{
+#if SDM_K1_OPT & 0x800000
+    if (fusion_tail_window(pjsj, rsj)) return fusion_tail_fast(pjsj, rsj);
+#endif
+    return fusion_tail_ref(pjsj, rsj);
 }
 
 // ---- the reference's "(double)x > 0.000001" / "< 0.000001" tests (PM.cc:345,497,510,560,662,705) ----------
@@ -1494,10 +1633,11 @@ __device__ __forceinline__ bool fuse_column(const float2* hyp, int stride, int n
     for (int b = 0; b < nh; b++) {
         if (!((bestmask >> b) & 1ull)) continue;
         float2 hb = hyp[b * stride];
-        fusion_accum(hb.x, hb.y, pjsj, rsj);
+        fusion_accum_decided(hb.x, hb.y, pjsj, rsj);
     }
-    rho_o = pjsj / rsj;
-    sigma_o = sqrtf(1 / rsj);
+    const float2 res = fusion_tail(pjsj, rsj);
+    rho_o = res.x;
+    sigma_o = res.y;
     return true;
 }
 

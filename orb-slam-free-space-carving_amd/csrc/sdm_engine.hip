@@ -2795,6 +2795,15 @@ int sdm_selftest(sdm_ctx* c, int which, unsigned long long out[2])
         hipLaunchKernelGGL(k_selftest_gates, dim3(4096), dim3(BLOCK), 0, c->stream, c->dprm, c->d_stats + 5, c->d_stats + 6);
     } else if (which == 11) {  // 2^32 operand pairs
         hipLaunchKernelGGL(k_selftest_quot_boxes, dim3(4096), dim3(BLOCK), 0, c->stream, 4096, c->d_stats + 5, c->d_stats + 6);
+    } else if (which == 13) {  // out[1] = undecided of ST_DEC_BLOCKS * BLOCK * ST13_ITERS plain draws
+        hipLaunchKernelGGL(k_selftest_ustar, dim3(ST_DEC_BLOCKS), dim3(BLOCK), 0, c->stream, c->dprm.inv_theta, ST13_ITERS,
+                           c->d_stats + 5, c->d_stats + 6);
+    } else if (which == 14) {  // ... of ST_DEC_BLOCKS * BLOCK * (ST14_ITERS / 20) * 210 plain terms
+        hipLaunchKernelGGL(k_selftest_fusion_decided, dim3(ST_DEC_BLOCKS), dim3(BLOCK), 0, c->stream, ST14_ITERS, c->d_stats + 5,
+                           c->d_stats + 6);
+    } else if (which == 15) {  // ... of ST_DEC_BLOCKS * BLOCK * ST15_ITERS plain draws
+        hipLaunchKernelGGL(k_selftest_fusion_tail, dim3(ST_DEC_BLOCKS), dim3(BLOCK), 0, c->stream, ST15_ITERS, c->d_stats + 5,
+                           c->d_stats + 6);
     } else if (which == 12) {  // the pair constants of the last compute call
         const sdm_ctx::TableKey& key = c->sets[c->cur_set].key;
         if (!key.valid || !key.has_consts || !c->d_pairs) return fail(SDM_EINVAL, "no pair constants staged");

@@ -362,9 +362,9 @@ __device__ __forceinline__ bool k1_fuse_counted(const float2* hyp, const float* 
         if (!((vm >> bb) & 1ull)) continue;
         const float2 hb = hyp[bb * K1_PX + p];
         const bool in = (bb == besta) ? (sa * sa > 0.0f) : chi_test_lazy(ha, hb, sa, &sgm[bb * K1_PX + p]);
-        if (in) fusion_accum(hb.x, sgm[bb * K1_PX + p], pjsj, rsj);
+        if (in) fusion_accum_decided(hb.x, sgm[bb * K1_PX + p], pjsj, rsj);
     }
-    result = make_float2(pjsj / rsj, sqrtf(1 / rsj));  // PM.cc:225-226
+    result = fusion_tail(pjsj, rsj);  // PM.cc:225-226
     return true;
 }
 
@@ -630,9 +630,9 @@ __global__ SDM_K1_LB void k_search_fuse(const float4* __restrict__ rec, long lon
                 float pjsj = 0.f, rsj = 0.f;
                 for (int bb = 0; bb < n; bb++) {
                     if (!((S0 >> bb) & 1ull)) continue;
-                    fusion_accum(hyp[bb * K1_PX + p].x, sgm[bb * K1_PX + p], pjsj, rsj);
+                    fusion_accum_decided(hyp[bb * K1_PX + p].x, sgm[bb * K1_PX + p], pjsj, rsj);
                 }
-                result = make_float2(pjsj / rsj, sqrtf(1 / rsj));  // PM.cc:225-226
+                result = fusion_tail(pjsj, rsj);  // PM.cc:225-226
                 n_fused = 1;
             }
         } else if (go) {
@@ -2187,6 +2187,203 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_pair_bits(const PairConst* _
     const unsigned long long v = ((cl & 8) ? 1ull : 0ull) | ((cl & 16) ? (1ull << 32) : 0ull);
     if (v) atomicAdd(bad, v);
     atomicAdd(tested, 1ull);
+}
+
+// which = 13, 14, 15: the decided f64 roundings (sdm_device.h decided_sum, SDM_K1_OPT bits 21-23) against the reference
+// statements, whatever bits the build has on.  bad = results that differ from the statement's bits (NaN against NaN passes);
+// undecided = PLAIN draws -- all inside the premise by construction, a fixed number per thread -- that the decided form
+// hands to the reference statement.  SPECIAL draws (window ends, operands outside the window, zeros, values next to a
+// rounding boundary) are compared the same way and are not part of the undecided count.
+constexpr int ST_DEC_BLOCKS = 1024;
+constexpr int ST13_ITERS = 512;  // plain draws per thread
+constexpr int ST14_ITERS = 120;  // chains per thread, lengths 1..20 in turn: 6 * 210 plain terms
+constexpr int ST15_ITERS = 1024;
+__device__ __forceinline__ bool st_same_bits(float a, float b)
+{
+    return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
+}
+__device__ __forceinline__ float st_mag(unsigned bits, unsigned e_lo, unsigned e_n, unsigned sign_mask)
+{
+    return __uint_as_float((bits & (0x007FFFFFu | sign_mask)) | ((e_lo + (bits >> 23) % e_n) << 23));  // 2^(e_lo-127) ..
+}
+// 13: ustar (PM.cc:455, 458).  Plain draws: best_pixel in [1, 638]; g, q, pe, ge log-uniform with every significand
+// (|g| in [2^-6, 2^7), |q| in [2^-6, 2^8), |pe|, |ge| in [2^-4, 2^8)) or, every other draw, on the lattices bilinear
+// interpolation of 8-bit rows produces (multiples of 1/8 .. 1/16; g != 0); denom as the statement forms it, always inside
+// [2^-30, 2^30).  Special draws: denom at both ends of that window, N = +-0, N next to k * denom, and N that puts
+// best_pixel + N/denom next to the midpoint of two floats.
+__global__ __launch_bounds__(BLOCK) void k_selftest_ustar(double inv_theta, int iters, unsigned long long* __restrict__ bad,
+                                                          unsigned long long* __restrict__ undecided)
+{
+    unsigned s = 0x9E3779B1u * (blockIdx.x * BLOCK + threadIdx.x + 1);
+    unsigned long long cnt = 0, und = 0;
+    const unsigned dwin_lo = 97u << 23;
+    for (int i = 0; i < iters; i++) {
+        const unsigned b0 = xs32(s), b1 = xs32(s), b2 = xs32(s), b3 = xs32(s), pick = xs32(s);
+        float g, q, pe, ge;
+        if (i & 1) {
+            g = (float)(1 + (int)(b0 % 1024u)) * ((b0 >> 31) ? -0.125f : 0.125f);
+            q = (float)((int)(b1 % 8193u) - 4096) * 0.0625f;
+            pe = (float)((int)(b2 % 2041u) - 1020) * 0.25f;
+            ge = (float)((int)(b3 % 8193u) - 4096) * 0.0625f;
+        } else {
+            g = st_mag(b0, 121u, 13u, 0x80000000u);
+            q = st_mag(b1, 121u, 14u, 0x80000000u);
+            pe = st_mag(b2, 123u, 12u, 0x80000000u);
+            ge = st_mag(b3, 123u, 12u, 0x80000000u);
+        }
+        const double c = (double)(1 + (int)((pick >> 8) % 638u));
+        const float gg = g * g;
+        float denom = (float)((double)gg + inv_theta * (double)q * (double)q);
+        const float gpe = g * pe;
+        double N = (double)gpe + inv_theta * (double)q * (double)ge;
+        {
+            float got;
+            const bool in = (__float_as_uint(denom) - dwin_lo) < (QB_DWIN_END - dwin_lo);
+            const bool ok = in && ustar_decided(c, N, denom, rcp_fast(denom), got);
+            if (!in || (ok && !st_same_bits(got, ustar_ref(c, N, denom)))) cnt++;
+            if (in && !ok) und++;
+        }
+        if ((pick & 7u) != 0) continue;
+        switch ((pick >> 3) & 7u) {
+        case 0: denom = 0x1p-30f; break;
+        case 1: denom = __uint_as_float(QB_DWIN_END - 1u); break;
+        case 2: N = 0.0; break;
+        case 3: N = -0.0; break;
+        case 4:
+        case 5: {  // next to k * denom, k up to 2^10: k * denom is exact in double
+            const double m = (double)(1 + (int)(b2 % 1024u)) * (double)denom;
+            N = __longlong_as_double(__double_as_longlong(m) + (long long)((b3 >> 4) % 5u) - 2ll);
+            if (b3 & 1u) N = -N;
+            break;
+        }
+        default: {  // c + N/denom next to the midpoint above a float near c + 2^-3 .. c + 2^3
+            const float f = (float)c + st_mag(b2, 124u, 6u, 0x80000000u);
+            const double mid = 0.5 * ((double)f + (double)__uint_as_float(__float_as_uint(f) + 1u));
+            const double m = (mid - c) * (double)denom;
+            N = __longlong_as_double(__double_as_longlong(m) + (long long)((b3 >> 4) % 9u) - 4ll);
+            break;
+        }
+        }
+        float got;
+        if (ustar_decided(c, N, denom, rcp_fast(denom), got) && !st_same_bits(got, ustar_ref(c, N, denom))) cnt++;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_down(cnt, o);
+        und += __shfl_down(und, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (cnt) atomicAdd(bad, cnt);
+        if (und) atomicAdd(undecided, und);
+    }
+}
+
+// 14: GetFusion's sums (PM.cc:936-937) over chains of 1..20 terms.  Plain terms: rho within 1 % of a base in [2^-4, 2^2),
+// sigma in [2^-15, 2^-4) with every significand; each term is applied to the REFERENCE's running sums by both forms.  One
+// special term per chain on top of its sums: sigma at both ends of the window [2^-50, 2^50) and just outside them, zero,
+// denormal, Inf, NaN and negative sigmas, zero / Inf / NaN / denormal rho -- through fusion_accum_decided, fallback included.
+__device__ __forceinline__ void fusion_accum_plain(float rho, float sg, float& pjsj, float& rsj)  // PM.cc:936-937 as written
+{
+    const double s2 = (double)sg * (double)sg;
+    pjsj = (float)((double)pjsj + (double)rho / s2);
+    rsj = (float)((double)rsj + 1.0 / s2);
+}
+__global__ __launch_bounds__(BLOCK) void k_selftest_fusion_decided(int iters, unsigned long long* __restrict__ bad,
+                                                                   unsigned long long* __restrict__ undecided)
+{
+    unsigned s = 0x85EBCA6Bu * (blockIdx.x * BLOCK + threadIdx.x + 1);
+    unsigned long long cnt = 0, und = 0;
+    const float sg_sp[10] = {0x1p-50f, __uint_as_float(FD_SG_END - 1u), __uint_as_float(FD_SG_LO - 1u), 0x1p50f, 0.f,
+                             1e-41f,   __builtin_inff(),                __builtin_nanf(""),             -0.01f,  3e-39f};
+    const float rho_sp[6] = {0.f, -0.f, __builtin_inff(), __builtin_nanf(""), 1e-41f, -0.5f};
+    for (int i = 0; i < iters; i++) {
+        const int len = 1 + i % 20;
+        const float base = st_mag(xs32(s), 123u, 6u, 0u);
+        float pjsj = 0.f, rsj = 0.f;
+        for (int t = 0; t < len; t++) {
+            const unsigned br = xs32(s), bs = xs32(s);
+            const float rho = base * (1.0f + 0.01f * ((float)(br >> 8) * (2.0f / 16777216.0f) - 1.0f));
+            const float sg = st_mag(bs, 112u, 11u, 0u);
+            float wp = pjsj, wr = rsj, gp = pjsj, gr = rsj;
+            fusion_accum_plain(rho, sg, wp, wr);
+            if (fusion_accum_try(rho, sg, gp, gr)) {
+                if (!st_same_bits(gp, wp) || !st_same_bits(gr, wr)) cnt++;
+            } else {
+                und++;
+            }
+            pjsj = wp;
+            rsj = wr;
+        }
+        const unsigned pick = xs32(s);
+        const float sg = sg_sp[pick % 10u];
+        const float rho = ((pick >> 8) & 1u) ? rho_sp[(pick >> 9) % 6u] : base;
+        float wp = pjsj, wr = rsj, gp = pjsj, gr = rsj;
+        fusion_accum_plain(rho, sg, wp, wr);
+        if (fusion_accum_try(rho, sg, gp, gr) && (!st_same_bits(gp, wp) || !st_same_bits(gr, wr))) cnt++;
+        gp = pjsj;
+        gr = rsj;
+        fusion_accum_decided(rho, sg, gp, gr);
+        if (!st_same_bits(gp, wp) || !st_same_bits(gr, wr)) cnt++;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_down(cnt, o);
+        und += __shfl_down(und, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (cnt) atomicAdd(bad, cnt);
+        if (und) atomicAdd(undecided, und);
+    }
+}
+
+// 15: GetFusion's result, pjsj / rsj and sqrtf(1 / rsj), in reciprocal form inside fusion_tail_window.  Plain draws: both
+// operands positive in [2^-40, 2^41), every significand -- all must take the reciprocal form (undecided counts those that
+// do not).  Special draws: all-ones significands, the window's ends and their outer neighbours, zeros of both signs, negative,
+// denormal, Inf and NaN operands, pjsj next to k * rsj.
+__global__ __launch_bounds__(BLOCK) void k_selftest_fusion_tail(int iters, unsigned long long* __restrict__ bad,
+                                                                unsigned long long* __restrict__ undecided)
+{
+    unsigned s = 0xC2B2AE3Du * (blockIdx.x * BLOCK + threadIdx.x + 1);
+    unsigned long long cnt = 0, und = 0;
+    const float sp[12] = {0.f,      -0.f,    1e-41f, __builtin_inff(), __builtin_nanf(""), -1.0f, __uint_as_float(QUOT_MAG_LO),
+                          __uint_as_float(QUOT_MAG_LO - 1u), __uint_as_float(QUOT_MAG_HI), __uint_as_float(QUOT_MAG_HI + 1u),
+                          0x1p-126f, 3e38f};
+    for (int i = 0; i < iters; i++) {
+        const unsigned ba = xs32(s), bb = xs32(s), pick = xs32(s);
+        float a = st_mag(ba, 87u, 81u, 0u), b = st_mag(bb, 87u, 81u, 0u);
+        {
+            const float2 want = fusion_tail_ref(a, b);
+            if (fusion_tail_window(a, b)) {
+                const float2 got = fusion_tail_fast(a, b);
+                if (!st_same_bits(got.x, want.x) || !st_same_bits(got.y, want.y)) cnt++;
+            } else {
+                und++;
+            }
+        }
+        if ((pick & 3u) != 0) continue;
+        switch ((pick >> 2) & 7u) {
+        case 0: a = __uint_as_float(__float_as_uint(a) | 0x7FFFFFu); break;
+        case 1: b = __uint_as_float(__float_as_uint(b) | 0x7FFFFFu); break;
+        case 2: a = __uint_as_float(__float_as_uint(a) | 0x7FFFFFu); b = __uint_as_float(__float_as_uint(b) | 0x7FFFFFu); break;
+        case 3: a = sp[(pick >> 8) % 12u]; break;
+        case 4: b = sp[(pick >> 8) % 12u]; break;
+        case 5: a = sp[(pick >> 8) % 12u]; b = sp[(pick >> 12) % 12u]; break;
+        default: {  // pjsj next to k * rsj (the quotient next to a rounding boundary); may leave the window: tested there too
+            const float k = (float)(1u + ((pick >> 8) & 255u));
+            a = __uint_as_float(__float_as_uint(k * b) + ((pick >> 16) & 3u) - 1u);
+            break;
+        }
+        }
+        const float2 want = fusion_tail_ref(a, b);
+        const float2 got = fusion_tail_window(a, b) ? fusion_tail_fast(a, b) : fusion_tail(a, b);
+        if (!st_same_bits(got.x, want.x) || !st_same_bits(got.y, want.y)) cnt++;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_down(cnt, o);
+        und += __shfl_down(und, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (cnt) atomicAdd(bad, cnt);
+        if (und) atomicAdd(undecided, und);
+    }
 }
 
 // which = 3: closed-form angle gates vs the reference statement, for d = theta2 - ref over
