@@ -1279,6 +1279,76 @@ typedef struct {
     long long small_components;/* out */
 } sdm_vmap_comp_args;
 int sdm_vmap_components(sdm_ctx *ctx, sdm_vmap_comp_args *args);
+/* Per-entry surface normals and surface variation of the voxel map: for every entry of a range, the unit normal of the plane
+ * through the stored points of the member entries in the (2r+1)^3 cells around it, the surface variation lambda_min /
+ * (lambda_0 + lambda_1 + lambda_2), and how many points went in; optionally oriented towards the camera of the entry's
+ * winning keyframe.  The semantics are this library's (tests/vmap_normals_np.py restates them) and are normative operation
+ * by operation: every output is bitwise reproducible.  It requires an open map and only reads it.
+ *   - Arithmetic: all of it is IEEE binary32: no fused multiply-add, the plain correctly rounded division and sqrtf,
+ *     denormals kept.  Each product is rounded before the add or subtract that takes it.
+ *   - Members: entry id is a MEMBER iff multiplicity[id] >= min_multiplicity and, when require_published != 0,
+ *     published[id] != 0 (if no classify has run every flag reads 0): the member test of sdm_vmap_components, word for
+ *     word.  The cell of an entry is c = floorf(P_k * inv) of its record point P, as sdm_vmap_components forms it.
+ *   - Samples: a member id with record point P visits the offsets d in {-r..r}^3, r = radius, in lexicographic order, dx
+ *     slowest and dz fastest; (0,0,0) is included and gives the entry itself.  A cell with a coordinate outside [-2^20,
+ *     2^20) holds nothing: the range test comes before the key is formed.  The cell's entry j is a sample iff it exists
+ *     and is a member.  Its coordinates are q_a = (xyz_j[a] - P[a]) * inv: one subtract, then one multiply.
+ *   - Sums: all sums start at +0 and accumulate in visiting order: k += 1; s_a = s_a + q_a; m_ab = m_ab + q_a*q_b for
+ *     (a,b) = (0,0),(0,1),(0,2),(1,1),(1,2),(2,2).  points[id - first] = k for a member and 0 for a non-member.
+ *   - Covariance: if k < min_points the entry is not estimated.  Otherwise kf = (float)k; mu_a = s_a / kf;
+ *     C_ab = m_ab / kf - mu_a*mu_b.
+ *   - Eigen-solve: A = C (symmetric), V = I; a cyclic Jacobi of exactly 6 sweeps that uses only + - x / sqrt.  Each sweep
+ *     takes the pairs (p,q) = (0,1), (0,2), (1,2) in that order; r is the third index.  If A_pq == 0 (-0 too) the pair does
+ *     nothing.  Else theta = (A_qq - A_pp) / (2*A_pq); t = copysignf(1, theta) / (fabsf(theta) + sqrtf(theta*theta + 1));
+ *     c = 1 / sqrtf(t*t + 1); s = t*c; h = t*A_pq; A_pp = A_pp - h; A_qq = A_qq + h; A_pq = +0; with x = A_rp, y = A_rq:
+ *     A_rp = c*x - s*y, A_rq = s*x + c*y; for i = 0,1,2 with x = V_ip, y = V_iq: V_ip = c*x - s*y, V_iq = s*x + c*y.
+ *     An overflowing theta*theta, or an infinite theta, gives t = +-0: the rotation is the identity and A_pq becomes 0;
+ *     this is no special case in code.
+ *   - Result: lambda_i = A_ii.  m = 0; if lambda_1 < lambda_m then m = 1; if lambda_2 < lambda_m then m = 2: ties go to
+ *     the lower index.  sum = (lambda_0 + lambda_1) + lambda_2; if !(sum > 0) the entry is not estimated.  Otherwise the
+ *     normal is column m of V, not renormalised, and variation = (lambda_m < 0 ? +0.0f : lambda_m) / sum.
+ *   - Orientation: the pose table is sdm_vmap_recarve's -- same checks, same camera centre O = -(Rwc * tcw) formed on the
+ *     host; n_poses == 0 is valid.  An estimated entry whose record tag is in the table is ORIENTED: d_a = O_a - P_a,
+ *     dot = (n_0*d_0 + n_1*d_1) + n_2*d_2, and if dot < 0 every component is negated.  A NaN dot does not flip, and the
+ *     entry still counts as oriented.  An estimated entry whose tag is absent keeps the sign the rotations left.
+ *   - Not estimated or non-member: normal = (+0,+0,+0) and variation = -1.0f.
+ *   - Range and destinations: the entries first .. first + count - 1 (count == -1: to M); outputs are indexed by
+ *     id - first.  normal holds 3 x capacity floats, variation and points capacity elements each, capacity >= the size of
+ *     the range; they follow args->on_device (there: 4-byte aligned).  Any of them may be NULL; all three NULL is valid
+ *     and returns the totals only.  An empty range queues nothing.
+ *   - Totals: entries = the size of the range; members, estimated and oriented are counted within the range.
+ *   - State: the call changes nothing.  Every output is a pure function of the arguments, the records (xyz, multiplicity,
+ *     tag) and the flags: bitwise the same from run to run, whatever the table layout and the slicing.
+ * Errors, all raised on the host before anything is queued; the four totals are then 0:
+ *   SDM_EINVAL: a NULL ctx or args.
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: radius not 1 or 2; min_points outside 3 .. (2*radius+1)^3; require_published not 0 or 1; first < 0,
+ *     count < -1, or first + count > M; a negative capacity; capacity below the range with any destination given; a
+ *     misaligned device pointer; the pose table's refusals: negative n_poses, NULL tags or Tcw with n_poses > 0, a tag
+ *     outside [0, 2^31), a tag listed twice.
+ *   SDM_EHIP: an allocation failure, raised before any launch.
+ * Cost: one lane per entry of the range; 27 or 125 read-only probes, on a hit 4 B of multiplicity (+ 1 B of flag) and 12 B
+ * of xyz; nine running sums and the Jacobi state in registers; no scratch per entry.  The pose table is uploaded once, 20 B
+ * per pose.  Host destinations pass through engine staging: one copy per array.  One host wait: the end, with 32 B of
+ * totals.  Measured: DESIGN.md s.28.
+ * Limits: O(range x (2r+1)^3) probes per call, not incremental; built on each voxel's winning point only; it goes stale
+ * with sdm_set_pose as the records do (sdm_vmap_repose re-places them); oriented by the winner's camera alone; one rank
+ * only. */
+typedef struct {
+    int radius;                /* in: 1 or 2 */
+    unsigned min_points;       /* in: 3 .. (2*radius+1)^3 */
+    unsigned min_multiplicity; /* in: as sdm_vmap_components */
+    int require_published;     /* in: 0 or 1 */
+    int on_device;             /* in: the three arrays are device pointers (4-byte aligned) */
+    long long first, count;    /* in: entries first .. first+count-1; count == -1: to M */
+    long long capacity;        /* in: elements each destination holds (normal: x3) */
+    float *normal;             /* [capacity][3] or NULL */
+    float *variation;          /* [capacity] or NULL */
+    unsigned *points;          /* [capacity] or NULL: the samples k of each entry */
+    long long entries, members, estimated, oriented;   /* out */
+} sdm_vmap_normal_args;
+int sdm_vmap_normals(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses], host*/,
+                     const float *Tcw /*[n_poses][12], host*/, sdm_vmap_normal_args *args);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

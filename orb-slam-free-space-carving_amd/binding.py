@@ -193,6 +193,14 @@ class VmapCompArgs(C.Structure):
                 ("small_components", C.c_longlong)]
 
 
+class VmapNormalArgs(C.Structure):
+    """sdm_vmap_normal_args"""
+    _fields_ = [("radius", C.c_int), ("min_points", C.c_uint), ("min_multiplicity", C.c_uint), ("require_published", C.c_int),
+                ("on_device", C.c_int), ("first", C.c_longlong), ("count", C.c_longlong), ("capacity", C.c_longlong),
+                ("normal", C.c_void_p), ("variation", C.c_void_p), ("points", C.c_void_p), ("entries", C.c_longlong),
+                ("members", C.c_longlong), ("estimated", C.c_longlong), ("oriented", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -242,6 +250,9 @@ VMAP_CAST_FIELDS = {"hit_id": np.uint32, "hit_step": np.int32, "hit_rho": np.flo
 VMAP_NO_COMPONENT = 0xFFFFFFFF
 VMAP_COMP_OUTS = ("entries", "members", "components", "largest", "small", "small_components")
 VMAP_COMP_FIELDS = ("label", "size", "small_ids")
+# sdm_vmap_normals: the outs, and the destinations with (dtype, values per entry)
+VMAP_NORMAL_OUTS = ("entries", "members", "estimated", "oriented")
+VMAP_NORMAL_FIELDS = {"normal": (np.float32, 3), "variation": (np.float32, 1), "points": (np.uint32, 1)}
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -326,6 +337,7 @@ SYMBOLS = [
     ("sdm_vmap_cast_segments", C.c_int, [_ctx, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(VmapCastArgs)]),
     ("sdm_vmap_render", C.c_int, [_ctx, _f32p, _f32p, C.c_int, C.c_int, C.c_float, C.POINTER(VmapCastArgs)]),
     ("sdm_vmap_components", C.c_int, [_ctx, C.POINTER(VmapCompArgs)]),
+    ("sdm_vmap_normals", C.c_int, [_ctx, C.c_int, _ip, _f32p, C.POINTER(VmapNormalArgs)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1746,6 +1758,54 @@ class Engine:
         res = {f: int(getattr(a, f)) for f in VMAP_COMP_OUTS}
         for f, w in dest.items():
             res[f] = w[:res["small"] if f == "small_ids" else res["entries"]]
+        return res
+
+    def vmap_normals(self, tags=None, Tcw=None, radius=1, min_points=3, min_multiplicity=0, require_published=False, first=0,
+                     count=None, normals=True, variations=True, counts=True):
+        """Per-entry surface normals of the voxel map (sdm_vmap_normals) for the entries first .. first + count - 1 (count
+        None: to the end).  An entry is a member if it has at least min_multiplicity points (and, with require_published,
+        is published); the plane is fitted to the stored points of the members in the (2 * radius + 1)^3 cells around a
+        member, if there are at least min_points of them.  tags int32[n] and Tcw float32[n, 12] (or None): an estimated
+        entry whose winning tag is listed has its normal turned towards that camera's centre.  Returns {"normal" float32[m,
+        3]: the unit normal, (0, 0, 0) where none was estimated; "variation" float32[m]: lambda_min / (lambda_0 + lambda_1 +
+        lambda_2), -1 where none was; "points" uint32[m]: the points that went in, 0 for a non-member; "entries", "members",
+        "estimated", "oriented"}, the arrays indexed by id - first.  normals / variations / counts: True -- a NumPy array is
+        made here; False -- not returned; or the destination, an array (pageable, or pinned from host_alloc) or a torch
+        device tensor of 4-byte elements (all of one kind).  A refusal raises SdmError.  The map is only read."""
+        tg = np.ascontiguousarray(np.asarray([] if tags is None else tags, dtype=np.int32).reshape(-1))
+        n = len(tg)
+        tp = pp = None
+        if n:
+            t12, pp = _f32(np.asarray(Tcw, dtype=np.float32).reshape(-1, 12))
+            if len(t12) != n:
+                raise ValueError("Tcw: need one row per tag")
+            tp = tg.ctypes.data_as(_ip)
+        a = VmapNormalArgs()
+        a.radius, a.min_points, a.min_multiplicity = int(radius), int(min_points), int(min_multiplicity)
+        a.require_published = int(require_published)
+        a.first, a.count = int(first), -1 if count is None else int(count)
+        m = None
+        kinds, dest, caps = set(), {}, []
+        for (f, (dt, per)), w in zip(VMAP_NORMAL_FIELDS.items(), (normals, variations, counts)):
+            if w is None or w is False:
+                continue
+            if w is True:
+                if m is None:
+                    m = max(self.vmap_info()["voxels"] - a.first if count is None else a.count, 1)
+                w = np.empty((m, per) if per > 1 else m, dt)
+            ptr, cap = self._dest(f, w, dt, per, kinds)
+            caps.append(cap)
+            setattr(a, f, ptr)
+            dest[f] = w
+        if len(kinds) > 1:
+            raise ValueError("the destinations mix host arrays and device tensors")
+        a.capacity = min(caps, default=0)
+        a.on_device = 1 if kinds == {"device"} else 0
+        self._check(self.lib.sdm_vmap_normals(self.ctx, n, tp, pp, C.byref(a)))
+        res = {f: int(getattr(a, f)) for f in VMAP_NORMAL_OUTS}
+        for f, w in dest.items():
+            per = VMAP_NORMAL_FIELDS[f][1]
+            res[f] = w.reshape(-1, per)[:res["entries"]] if per > 1 else w.reshape(-1)[:res["entries"]]
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):
