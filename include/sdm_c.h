@@ -1539,7 +1539,13 @@ int sdm_get_timing(sdm_ctx *ctx, double ms_total[SDM_NUM_STAGES], long long laun
  * which 13, 14, 15: K1's decided f64 roundings vs the statements as written -- 13 ustar (PM.cc:458), 14 GetFusion's two
  *          sums over chains of 1..20 terms (PM.cc:936-937), 15 GetFusion's pjsj / rsj and sqrtf(1 / rsj) (PM.cc:225-226);
  *          out[1] = draws inside the operand window that were handed to the statement (undecided), out of
- *          2^27 (13), 330301440 (14) and 2^28 (15) such draws; draws outside the windows and special operands on top. */
+ *          2^27 (13), 330301440 (14) and 2^28 (15) such draws; draws outside the windows and special operands on top;
+ * which 16, 17, 18: no arithmetic -- where the keys of a hash table sit, for tests that force long probes: out[0] = the
+ *          largest (slot - home) & mask over the occupied slots, home = the key's hash & mask; out[1] = occupied slots with
+ *          slot < home, i.e. keys whose probe went past the end of the table.  16 the voxel map's table, 17 its observation
+ *          set (0, 0 before the first observation), both SDM_ESTATE without an open map; 18 the per-call table the last
+ *          sdm_extract_points_voxel* call with a plain point left in the context's scratch (SDM_ESTATE: none).  Read-only:
+ *          nothing any other call returns depends on them. */
 int sdm_selftest(sdm_ctx *ctx, int which, unsigned long long out[2]);
 /* name of the device the context runs on, e.g. "gfx950" */
 const char *sdm_device_arch(sdm_ctx *ctx);

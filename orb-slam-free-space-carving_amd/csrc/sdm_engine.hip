@@ -267,6 +267,8 @@ struct sdm_ctx {
     // host destinations; each grows on demand
     unsigned char* d_vox = nullptr;
     size_t vox_bytes = 0;
+    const unsigned long long* vox_last_keys = nullptr;  // the last call's table keys in d_vox (sdm_selftest(18) reads them)
+    unsigned long long vox_last_cap = 0;
     unsigned char* d_vox_out = nullptr;
     size_t vox_out_bytes = 0;
     // sdm_extract_points_voxel_cameras (sdm_voxcam.h): camera table, ranks, bitsets, tile counts and offsets; staging of
@@ -2813,6 +2815,22 @@ int sdm_selftest(sdm_ctx* c, int which, unsigned long long out[2])
         const int np = key.n_ref * key.n;
         hipLaunchKernelGGL(k_selftest_pair_bits, dim3((np + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d_pairs, np,
                            c->d_stats + 5, c->d_stats + 6);
+    } else if (which == 16 || which == 17 || which == 18) {  // no arithmetic: where the keys of a table sit
+        const unsigned long long* keys = nullptr;
+        unsigned long long cap = 0;
+        if (which == 18) {
+            if (!c->vox_last_keys) return fail(SDM_ESTATE, "no per-call voxel table: sdm_extract_points_voxel* first");
+            keys = c->vox_last_keys, cap = c->vox_last_cap;
+        } else {
+            if (!c->vmap.open) return fail(SDM_ESTATE, "no open voxel map");
+            if (which == 16) keys = c->vmap.tb.keys, cap = c->vmap.cap;
+            else if (c->vmap.obs.d_table) keys = c->vmap.obs.tb.keys, cap = c->vmap.obs.cap;  // (no set yet: 0, 0)
+        }
+        if (cap)
+            launch_sliced(c, (long long)((cap + BLOCK - 1) / BLOCK), [&](long long b0, unsigned g) {
+                hipLaunchKernelGGL(k_selftest_table_layout, dim3(g), dim3(BLOCK), 0, c->stream, keys, cap,
+                                   (unsigned long long)b0 * BLOCK, c->d_stats + 5);
+            });
     } else {
         return fail(SDM_EINVAL, "unknown selftest");
     }

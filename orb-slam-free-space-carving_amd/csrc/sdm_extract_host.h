@@ -356,6 +356,7 @@ int voxel_merge(VoxelCall& v, int source, double max_sigma, double min_rho)
     v.vt = ext_tiles(T);
     v.pblocks = (T + BLOCK - 1) / BLOCK;
     VoxTable& tb = v.tb;
+    c->vox_last_keys = nullptr;  // (the scratch may move)
     if ((rc = carve_scratch(&c->d_vox, &c->vox_bytes, [&](Carver& k) {
              tb.keys = k.take<unsigned long long>((size_t)cap);
              tb.vals = k.take<unsigned long long>((size_t)cap);
@@ -370,6 +371,7 @@ int voxel_merge(VoxelCall& v, int source, double max_sigma, double min_rho)
                             ext_grow_host)))
         return rc;
     tb.mask = cap - 1;
+    c->vox_last_keys = tb.keys, c->vox_last_cap = cap;
     const auto bytes_to = [](const void* from, const void* to) { return (size_t)((const unsigned char*)to - (const unsigned char*)from); };
     HIP_TRY(hipMemsetAsync(tb.keys, 0xff, bytes_to(tb.keys, tb.cnt), c->stream));  // keys: VOX_EMPTY; values: the minimum's identity
     HIP_TRY(hipMemsetAsync(tb.cnt, 0, bytes_to(tb.cnt, tb.rank), c->stream));      // counts and the flag

@@ -289,4 +289,27 @@ __global__ __launch_bounds__(BLOCK) void k_vobs_list_fill(VobsLog lg, const unsi
     }
 }
 
+// sdm_selftest(16), (17), (18): how far the table's keys sit from home.  One lane per slot s0 + thread of `keys`, read-only:
+// out[0] = max over the occupied slots of (slot - home) & mask, out[1] = occupied slots below their home (the key's probe
+// went past the table's end).  Serves the map's table, the observation set and the per-call table: all hash with vox_mix.
+__global__ __launch_bounds__(BLOCK) void k_selftest_table_layout(const unsigned long long* __restrict__ keys,
+                                                                 unsigned long long cap, unsigned long long s0,
+                                                                 unsigned long long* __restrict__ out)
+{
+    const unsigned long long s = s0 + (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    unsigned long long disp = 0;
+    bool wrapped = false;
+    if (s < cap) {
+        const unsigned long long key = keys[s];
+        if (key != VOX_EMPTY) {
+            const unsigned long long home = vox_mix(key) & (cap - 1);
+            disp = (s - home) & (cap - 1);
+            wrapped = s < home;
+        }
+    }
+    if (disp) atomicMax(&out[0], disp);
+    const unsigned long long wm = __ballot(wrapped);  // (every lane of the wave arrives here)
+    if (wm && (threadIdx.x & 63) == 0) atomicAdd(&out[1], (unsigned long long)__popcll(wm));
+}
+
 }  // namespace sdm
