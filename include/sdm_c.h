@@ -1349,6 +1349,78 @@ typedef struct {
 } sdm_vmap_normal_args;
 int sdm_vmap_normals(sdm_ctx *ctx, int n_poses, const int *tags /*[n_poses], host*/,
                      const float *Tcw /*[n_poses][12], host*/, sdm_vmap_normal_args *args);
+/* A triangle mesh of the voxel map's entries, stitched on the device: every OWNER -- a member at the bottom of its run of
+ * members along the dominant axis of its normal -- joins the local height field over its own cell: itself, the
+ * representative of the next column along u, of the next along v, and of the diagonal one.  A triangle is three entry ids;
+ * a consumer takes the vertex positions from the records (sdm_vmap_fetch).  The semantics are this library's
+ * (tests/vmap_mesh_np.py restates them); every output is an integer decided by comparisons and bitwise reproducible.  It
+ * requires an open map and only reads it.
+ *   - Members: entry id is a MEMBER iff multiplicity[id] >= min_multiplicity and, when require_published != 0,
+ *     published[id] != 0 (if no classify has run every flag reads 0): the member test of sdm_vmap_components, word for
+ *     word.  The cell of an entry is c = floorf(P_k * inv) of its record point P, as sdm_vmap_components forms it.  A cell
+ *     with a coordinate outside [-2^20, 2^20) holds nothing: the range test comes before the key is formed.  Below, "the
+ *     member of a cell" is the cell's entry if it exists and is a member.
+ *   - Input normal: normal[(id - first)*3 + 0..2] is caller-supplied binary32, normally the output of sdm_vmap_normals over
+ *     the same range.  It is only compared, never used in arithmetic.  The axis: a = 0; if (fabsf(n_1) > fabsf(n_a)) a = 1;
+ *     if (fabsf(n_2) > fabsf(n_a)) a = 2: ties go to the lower index and a NaN never wins.  Denormals are kept: a denormal
+ *     component is > 0.  u = (a+1) mod 3 and v = (a+2) mod 3.
+ *   - Owner: entry id of the range is an OWNER iff it is a member, fabsf(n_a) > 0 (false for a NaN, so an all-zero or
+ *     NaN-at-a normal owns nothing), and the cell c - e_a holds no member: it is the bottom of its run along a.
+ *   - Step: step(j, ax) for ax in {u, v}, in the owner's frame: t = cell(j) + e_ax; for da in the order 0, -1, +1: if the
+ *     cell t + da*e_a holds a member k, then at most twice: if the cell below it along -e_a holds a member, take that one
+ *     and move down; return the result.  No hit gives NONE.
+ *   - Corners: Nu = step(id, u); Nv = step(id, v); C = step(Nu, v) if Nu exists; if C is NONE and Nv exists, C =
+ *     step(Nv, u).  The four lie in four distinct columns, so they are distinct ids.
+ *   - Triangles of an owner, in this order: all three exist: (id,Nu,C), (id,C,Nv), a QUAD; only Nu and Nv: (id,Nu,Nv);
+ *     only Nu and C: (id,Nu,C); only Nv and C: (id,C,Nv), each a SINGLE; otherwise none.  If n_a < 0 the second and third
+ *     index of each triangle are swapped: the winding turns towards the normal.
+ *   - Outputs: tri, [T][3]: the triangles of the owners in ascending id, an owner's first triangle before its second.
+ *     owner_tris[id - first] in {0, 1, 2}.  vertex_used[j], j in [0, M): 1 iff j is a corner of a triangle of this call,
+ *     else 0.
+ *   - Totals: entries = the size of the range; members and owners are counted within the range; quads; singles;
+ *     triangles = 2*quads + singles; vertices = the ones of vertex_used, counted even when that pointer is NULL.
+ *   - Range: the entries first .. first + count - 1 (count == -1: to M).  A sub-range returns exactly the whole call's
+ *     triangles whose owner lies in it, in order.  An empty range queues nothing and writes no destination.
+ *   - Capacity: normal holds 3 x capacity floats and owner_tris capacity bytes, capacity >= the size of the range;
+ *     vertex_used holds used_capacity >= M bytes; tri holds 3 x tri_capacity words.  triangles > tri_capacity with tri !=
+ *     NULL is SDM_EINVAL; the seven totals are filled and no destination is written (sdm_vmap_classify's and
+ *     sdm_vmap_components' contract: counts first, one wait, and the writing launch is queued only if the call is not
+ *     refused).  The caller sizes the array and calls again.  The arrays follow args->on_device (there: normal and tri
+ *     4-byte aligned).  Any destination may be NULL; all three NULL is valid and returns the totals only.
+ *   - State: the call changes nothing in the map or the engine.  Every output is a pure function of the arguments, the
+ *     records' cells and multiplicities, and the flags: bitwise the same from run to run, whatever the table layout and the
+ *     slicing.
+ * Errors, all raised on the host before anything is queued; the seven totals are then 0:
+ *   SDM_EINVAL: a NULL ctx or args.
+ *   SDM_ESTATE: no open map.
+ *   SDM_EINVAL: require_published not 0 or 1; first < 0, count < -1, or first + count > M; a NULL normal with a range that
+ *     is not empty; a negative capacity, tri_capacity or used_capacity; capacity below the range; used_capacity < M with
+ *     vertex_used given; a misaligned device pointer.
+ *   SDM_EHIP: an allocation failure, raised before any launch.
+ * Cost: one lane per entry of the range; 12 B of normal, and per owner at most 21 read-only probes (1 + 4 x (3 + 2)), each
+ * hit 4 B of multiplicity (+ 1 B of flag); then two passes in tiles for the count and the write, and one over M bytes for
+ * the vertices.  Scratch: 13 B per entry of the range and 1 B per entry of the map.  Host normals are staged in, host
+ * destinations pass through engine staging: one copy per array of exactly the range (tri: triangles, vertex_used: M)
+ * elements.  Two host waits: the totals (56 B), then the end.  Measured: DESIGN.md s.29.
+ * Limits: the mesh is voxel-level, at each voxel's winning point; the vertices are the run bottoms only; a missing owner
+ * corner loses that cell's triangle; there are seams where the dominant axis changes; the mesh is not watertight; a surface
+ * at 45 degrees to two axes (a double tie of the normal's components) is the bad case; the call is O(range) per call, not
+ * incremental; the result goes stale with sdm_set_pose as the records do (sdm_vmap_repose re-places them); one rank only. */
+typedef struct {
+    unsigned min_multiplicity; /* in: as sdm_vmap_components */
+    int require_published;     /* in: 0 or 1 */
+    int on_device;             /* in: the four arrays are device pointers (normal, tri: 4-byte aligned) */
+    long long first, count;    /* in: entries first .. first+count-1; count == -1: to M */
+    long long capacity;        /* in: entries normal (x3) and owner_tris hold */
+    long long tri_capacity;    /* in: triangles tri holds */
+    long long used_capacity;   /* in: bytes vertex_used holds */
+    const float *normal;       /* in: [capacity][3] */
+    unsigned *tri;             /* [tri_capacity][3] or NULL */
+    unsigned char *owner_tris; /* [capacity] or NULL */
+    unsigned char *vertex_used;/* [used_capacity] or NULL */
+    long long entries, members, owners, quads, singles, triangles, vertices;   /* out */
+} sdm_vmap_mesh_args;
+int sdm_vmap_mesh(sdm_ctx *ctx, sdm_vmap_mesh_args *args);
 /* The most points sdm_extract_points can return for these arguments: the list length of each slot it walks by list,
  * W x H of the others (for sizing buffers without a second call).  Same slot errors; host-blocking only as above. */
 int sdm_extract_bound(sdm_ctx *ctx, int n, const int *slots, int source, double min_rho, long long *bound);

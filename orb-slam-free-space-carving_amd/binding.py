@@ -201,6 +201,15 @@ class VmapNormalArgs(C.Structure):
                 ("members", C.c_longlong), ("estimated", C.c_longlong), ("oriented", C.c_longlong)]
 
 
+class VmapMeshArgs(C.Structure):
+    """sdm_vmap_mesh_args"""
+    _fields_ = [("min_multiplicity", C.c_uint), ("require_published", C.c_int), ("on_device", C.c_int), ("first", C.c_longlong),
+                ("count", C.c_longlong), ("capacity", C.c_longlong), ("tri_capacity", C.c_longlong),
+                ("used_capacity", C.c_longlong), ("normal", C.c_void_p), ("tri", C.c_void_p), ("owner_tris", C.c_void_p),
+                ("vertex_used", C.c_void_p), ("entries", C.c_longlong), ("members", C.c_longlong), ("owners", C.c_longlong),
+                ("quads", C.c_longlong), ("singles", C.c_longlong), ("triangles", C.c_longlong), ("vertices", C.c_longlong)]
+
+
 # sdm_extract_points fields: (dtype, values per point)
 POINT_FIELDS = {"xyz": (np.float32, 3), "pixel": (np.uint32, 1), "rho_sigma": (np.float32, 2), "intensity": (np.uint8, 1)}
 
@@ -253,6 +262,9 @@ VMAP_COMP_FIELDS = ("label", "size", "small_ids")
 # sdm_vmap_normals: the outs, and the destinations with (dtype, values per entry)
 VMAP_NORMAL_OUTS = ("entries", "members", "estimated", "oriented")
 VMAP_NORMAL_FIELDS = {"normal": (np.float32, 3), "variation": (np.float32, 1), "points": (np.uint32, 1)}
+# sdm_vmap_mesh: the outs, and the destinations with (dtype, values per element)
+VMAP_MESH_OUTS = ("entries", "members", "owners", "quads", "singles", "triangles", "vertices")
+VMAP_MESH_FIELDS = {"tri": (np.uint32, 3), "owner_tris": (np.uint8, 1), "vertex_used": (np.uint8, 1)}
 
 # every symbol include/sdm_c.h declares: (name, restype, argtypes)
 _f32p, _u8p, _ip = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
@@ -338,6 +350,7 @@ SYMBOLS = [
     ("sdm_vmap_render", C.c_int, [_ctx, _f32p, _f32p, C.c_int, C.c_int, C.c_float, C.POINTER(VmapCastArgs)]),
     ("sdm_vmap_components", C.c_int, [_ctx, C.POINTER(VmapCompArgs)]),
     ("sdm_vmap_normals", C.c_int, [_ctx, C.c_int, _ip, _f32p, C.POINTER(VmapNormalArgs)]),
+    ("sdm_vmap_mesh", C.c_int, [_ctx, C.POINTER(VmapMeshArgs)]),
     ("sdm_extract_bound", C.c_int, [_ctx, C.c_int, _ip, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     ("sdm_depth_pool_ptr", C.c_void_p, [_ctx]),
     ("sdm_assume_pipeline_maps", C.c_int, [_ctx, C.c_int, _ip]),
@@ -1806,6 +1819,76 @@ class Engine:
         for f, w in dest.items():
             per = VMAP_NORMAL_FIELDS[f][1]
             res[f] = w.reshape(-1, per)[:res["entries"]] if per > 1 else w.reshape(-1)[:res["entries"]]
+        return res
+
+    def vmap_mesh(self, normal, min_multiplicity=0, require_published=False, first=0, count=None, tri=True, owner_tris=True,
+                  vertex_used=True, tri_capacity=None):
+        """A triangle mesh of the voxel map's entries first .. first + count - 1 (count None: to the end), stitched on the
+        device (sdm_vmap_mesh).  normal float32[m, 3]: the entries' normals, normally vmap_normals(...)["normal"] over the
+        same range -- an array, or a torch device tensor (then every destination given is one too).  An entry is a member if
+        it has at least min_multiplicity points (and, with require_published, is published); a member at the bottom of its
+        run along its normal's dominant axis owns up to two triangles over its cell.  Returns {"tri" uint32[T, 3]: entry
+        ids, the owners ascending; "owner_tris" uint8[m]: 0, 1 or 2; "vertex_used" uint8[M]: 1 for a corner of a triangle;
+        "entries", "members", "owners", "quads", "singles", "triangles", "vertices"}.  tri / owner_tris / vertex_used: True
+        -- a NumPy array is made here (for tri, without tri_capacity, after one call for the totals); False -- not returned;
+        or the destination, an array or a device tensor of that element size.  tri_capacity: the triangles a tri made here
+        holds.  A tri too short raises SdmError with the seven totals as attributes; nothing has been written then.  The map
+        is only read."""
+        a = VmapMeshArgs()
+        a.min_multiplicity, a.require_published = int(min_multiplicity), int(require_published)
+        a.first, a.count = int(first), -1 if count is None else int(count)
+        kinds = set()
+        if not hasattr(normal, "is_cuda"):
+            normal = np.ascontiguousarray(np.asarray(normal, dtype=np.float32))
+        ptr, rows = self._dest("normal", normal, np.float32, 3, kinds)
+        on_device = kinds == {"device"}
+        a.normal, a.capacity, a.on_device = (ptr if rows else None), rows, int(on_device)
+        M = self.vmap_info()["voxels"]
+
+        def call():
+            rc = self.lib.sdm_vmap_mesh(self.ctx, C.byref(a))
+            if rc:
+                e = SdmError(rc, self.lib.sdm_last_error().decode())
+                for f in VMAP_MESH_OUTS:
+                    setattr(e, f, int(getattr(a, f)))
+                raise e
+
+        def make(shape, dt):
+            if not on_device:
+                return np.zeros(shape, dt)
+            import torch  # (a device tensor was passed in: torch is loaded)
+            return normal.new_zeros(shape, dtype=torch.int32 if dt is np.uint32 else torch.uint8)
+
+        dest = {}
+        for (f, (dt, per)), w in zip(VMAP_MESH_FIELDS.items(), (tri, owner_tris, vertex_used)):
+            if w is None or w is False:
+                continue
+            if w is True:
+                if f == "tri":
+                    if tri_capacity is None:
+                        call()   # the totals only: no destination is set yet
+                        tri_capacity = a.triangles
+                    w = make((max(int(tri_capacity), 1), 3), dt)
+                else:
+                    w = make(max(M if f == "vertex_used" else rows, 1), dt)
+            ptr, cap = self._dest(f, w, dt, per, kinds)
+            if f == "tri":
+                a.tri_capacity = cap
+            elif f == "vertex_used":
+                a.used_capacity = cap
+            else:
+                a.capacity = min(rows, cap)
+            setattr(a, f, ptr)
+            dest[f] = w
+        if len(kinds) > 1:
+            raise ValueError("normal and the destinations mix host arrays and device tensors")
+        call()
+        res = {f: int(getattr(a, f)) for f in VMAP_MESH_OUTS}
+        for f, w in dest.items():
+            if f == "tri":
+                res[f] = w.reshape(-1, 3)[:res["triangles"]]
+            else:
+                res[f] = w.reshape(-1)[:M if f == "vertex_used" else res["entries"]]
         return res
 
     def extract_bound(self, slots, source=1, min_rho=1e-6):

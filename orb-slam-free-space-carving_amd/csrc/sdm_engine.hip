@@ -50,6 +50,8 @@
 #include "sdm_vmap_comp_check.h"
 #include "sdm_vmap_normals.h"
 #include "sdm_vmap_normals_check.h"
+#include "sdm_vmap_mesh.h"
+#include "sdm_vmap_mesh_check.h"
 
 using namespace sdm;
 
@@ -2237,6 +2239,7 @@ int sdm_download_pointset(sdm_ctx* c, int slot, float* xyz)
 #include "sdm_vmap_cast_host.h"
 #include "sdm_vmap_comp_host.h"
 #include "sdm_vmap_normals_host.h"
+#include "sdm_vmap_mesh_host.h"
 
 void* sdm_depth_pool_ptr(sdm_ctx* c) { return c ? (void*)c->pool : nullptr; }
 
