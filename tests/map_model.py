@@ -15,6 +15,16 @@ alone.  Nothing here touches an engine, and nothing here imports torch.
   refusals       SDM_ESTATE without an open map for every new call, SDM_EINVAL for a tag listed twice (repose, retire,
                  recarve), ratio_den == 0, a recarve range beyond E, and the slot and neighbour states observe inherits;
                  each steered into every sequence; a refused call leaves the model untouched
+  queries        the five read-only calls (QUERY_OPS: cast_segments, render, components, normals, mesh) come from a stream
+                 of their own beside the main one (QueryStream: a second RNG, the counters MapWorld.qcov): with them
+                 filtered out a sequence is the one generated without them.  MapWorld.apply answers them through
+                 vmap_cast_np, vmap_comp_np, vmap_normals_np and vmap_mesh_np on the model's own records, flags ("none yet"
+                 before the first committing classify of the map) and voxel size, and changes nothing.  Their refusals:
+                 SDM_ESTATE without a map for each, SDM_EINVAL for require_published 2, a connectivity that is none of the
+                 three, radius 3, a range beyond M, a tag listed twice, and a small_ids / tri destination one element short
+                 (refused with the totals).  check_query_coverage holds the conditions on the stream; its sensitivity
+                 counters count the queries whose answer differs on the state before the last change (sens_query_stale)
+                 and with every flag cleared (sens_query_flags)
 
 MapWorld.apply(op, args) applies one call and returns what the engine must answer; it keeps the coverage counters that
 check_coverage asserts (conditions on the sequences, not on an engine) and the sensitivity counters, each the number of
@@ -23,8 +33,13 @@ import copy
 
 import numpy as np
 
+import carve_np
 import cloud_model as cm
+import vmap_cast_np as vk
+import vmap_comp_np as vq
 import vmap_import_np as vi
+import vmap_mesh_np as vms
+import vmap_normals_np as vn
 import vmap_recarve_np as vrc
 import vmap_repose_np as vrp
 import vmap_retire_np as vrt
@@ -64,6 +79,23 @@ _WEIGHT = dict({o: (1.2 if o.startswith("pointset") else 0.55) * cm._WEIGHT[o] f
                vmap_fetch=1, vmap_fetch_evidence=1, vmap_fetch_cameras=1, vmap_fetch_published=1)
 
 
+# ---- the read-only queries: a stream of their own beside the main one (generate) ---------------------------------------
+QUERY_OPS = ("vmap_cast_segments", "vmap_render", "vmap_components", "vmap_normals", "vmap_mesh")
+QKINDS = tuple(o[5:] for o in QUERY_OPS)
+QARRAYS = {"vmap_cast_segments": ("hit_id", "hit_step"), "vmap_render": ("hit_id", "hit_step", "hit_rho"),
+           "vmap_components": vq.ARRAYS, "vmap_normals": vn.ARRAYS, "vmap_mesh": vms.ARRAYS}
+QTOTALS = {"vmap_cast_segments": vk.OUTS, "vmap_render": vk.OUTS, "vmap_components": vq.OUTS, "vmap_normals": vn.OUTS,
+           "vmap_mesh": vms.OUTS}
+QEVENTS = ("repose", "retire", "classify")  # a query straight behind one of them (retire and classify: committing)
+QFIRST = ("clear", "import", "set_pose", "big")  # further events whose first occurrence is followed by every query kind
+QINVALID = ("published2", "connectivity", "radius", "range", "twice", "small_short", "tri_short")
+QREFUSALS = tuple("refuse_no_map_" + k for k in QKINDS) + tuple("refuse_" + r for r in QINVALID)
+QCONTENT = ("rays_hit", "rays_miss", "rays_skipped", "render_hit_and_zero", "comp_rich", "normals_rich", "mesh_quads_singles",
+            "mesh_empty", "mesh_from_normals", "mesh_crafted")
+QPER_KIND = ("n", "sens_query_stale", "sens_query_flags", "pub_before", "pub_after") + tuple("after_" + e for e in QEVENTS)
+BIG = 50  # the main generator keeps a map of this many entries alive while its content conditions are open
+
+
 class FullMirror(Mirror):
     """test_gpu_vmap_class.Mirror fed the model's clouds (cloud_model.MapMirror's two feeds)"""
     integrate_cloud = cm.MapMirror.integrate_cloud
@@ -83,6 +115,20 @@ def jolt(rng, T, shift=0.02):
     return np.concatenate([R @ T[:, :3], (R @ T[:, 3] + rng.normal(0, shift, 3)).reshape(3, 1)], axis=1).astype(F)
 
 
+def _same_state(x, y):
+    """two states of MapWorld._query_state's kind hold the same bits"""
+    if x is None or y is None:
+        return x is y
+    return x[2] == y[2] and (x[1] is None) == (y[1] is None) and (x[1] is None or x[1].tobytes() == y[1].tobytes()) and \
+        all(x[0][f].tobytes() == y[0][f].tobytes() for f in x[0])
+
+
+def _differs(op, x, y):
+    """two answers of a query differ in a total or in a byte of an array"""
+    return any(x[f] != y[f] for f in QTOTALS[op]) or \
+        any(x[f].shape != y[f].shape or x[f].tobytes() != y[f].tobytes() for f in QARRAYS[op])
+
+
 class MapWorld(cm.World):
     def __init__(self, oracle, seq, lam=8.0):
         super().__init__(oracle, seq, lam)
@@ -99,6 +145,14 @@ class MapWorld(cm.World):
              "retire_unobserved_both", "retire_orphaned", "grown_after_repose", "grown_after_retire", "recarve_chain",
              "carry_repose_published", "carry_retire_published", "recarve_unposed", "recarve_short", "pairs_created",
              "max_pairs") + SENS, 0)
+        # the queries' own counters: nothing of the main stream's (count, cov, mcov, last) is touched by a query
+        self.qcov = dict.fromkeys(("calls", "refusals") + QREFUSALS + QCONTENT + tuple("first_" + e for e in QFIRST) +
+                                  tuple("%s_%s" % (p, k) for p in QPER_KIND for k in QKINDS), 0)
+        self.qnow = self.qprev = None  # what the queries read, now and before the last call that changed it
+        self.qlast = None              # the last call of the main stream that was not refused: (op, it committed)
+        self.qapplied = False          # the main stream's last call was not refused
+        self.qchanged = False          # that call changed what the queries read
+        self.qnormal = None            # the last vmap_normals of the state as it stands: (its range and filters, the normals)
         self._map_reset()
 
     # -- tags and the caller's pose table
@@ -150,6 +204,8 @@ class MapWorld(cm.World):
 
     # -- refusals
     def refusal(self, op, a):
+        if op in QUERY_OPS:
+            return self._query_refusal(op, a)
         if op not in NEW_OPS:
             return super().refusal(op, a)
         if self.map is None:
@@ -166,6 +222,19 @@ class MapWorld(cm.World):
 
     # -- one call
     def apply(self, op, a):
+        if op in QUERY_OPS:
+            return self._query(op, a)
+        res = self._apply(op, a)
+        if not res.get("refused"):
+            self.qlast = (op, bool(a.get("commit", True)) if op in ("vmap_classify", "vmap_retire") else True)
+        cur = self._query_state()
+        self.qapplied = not res.get("refused")
+        self.qchanged = not _same_state(cur, self.qnow)
+        if self.qchanged:
+            self.qprev, self.qnow, self.qnormal = self.qnow if cur is not None else None, cur, None
+        return res
+
+    def _apply(self, op, a):
         if op in NEW_OPS:
             self.count[op] += 1
             res = self._map(op, a)
@@ -221,6 +290,104 @@ class MapWorld(cm.World):
             if kind == "no_depth":
                 self.cov["hist_reupload"] += sum("reupload" in self.history(k) for k in a["slots"])
         return {"refused": ref[0]}
+
+    # -- the read-only queries
+    def _query_state(self):
+        """what the five queries read, as copies: (records, flags or None before the first committing classify, voxel size)"""
+        mp = self.map
+        if mp is None:
+            return None
+        M = mp.vm.M
+        rec = {f: mp.vm.rec[f][:M].copy() for f in ("xyz", "multiplicity", "tag")}
+        return rec, (mp.cl.flags(M).copy() if mp.cl.calls else None), mp.voxel
+
+    def _query_refusal(self, op, a):
+        if self.map is None:
+            return ESTATE, "no_map"
+        M = self.map.vm.M
+        if a["require_published"] not in (0, 1):
+            return EINVAL, "published2"
+        if op == "vmap_components" and a["connectivity"] not in vq.MAX_L1:
+            return EINVAL, "connectivity"
+        if op == "vmap_normals" and a["radius"] not in (1, 2):
+            return EINVAL, "radius"
+        if op in ("vmap_normals", "vmap_mesh") and a["first"] + (0 if a["count"] is None else a["count"]) > M:
+            return EINVAL, "range"
+        if op == "vmap_normals" and a["tags"] is not None and len(set(a["tags"])) != len(a["tags"]):
+            return EINVAL, "twice"
+        if a.get("short"):  # a small_ids / tri destination one element short of what the call would fill
+            return EINVAL, "small_short" if op == "vmap_components" else "tri_short"
+        return None
+
+    @staticmethod
+    def answer(op, a, state):
+        """the restatement of the call on a state of _query_state's kind"""
+        rec, flags, voxel = state
+        flt = dict(min_multiplicity=a["min_multiplicity"], require_published=bool(a["require_published"]))
+        if op in ("vmap_cast_segments", "vmap_render"):
+            flt.update(start_margin=a["start_margin"], end_margin=a["end_margin"], max_steps=a["max_steps"])
+            if op == "vmap_render":
+                return vk.render(rec, flags, a["K"], a["T"], a["W"], a["H"], a["rho_far"], voxel, **flt)
+            return vk.cast_segments(rec, flags, a["origins"], a["ends"], voxel, **flt)
+        if op == "vmap_components":
+            return vq.components(rec, flags, voxel, connectivity=a["connectivity"], min_size=a["min_size"], **flt)
+        if op == "vmap_normals":
+            return vn.normals(rec, flags, voxel, tags=a["tags"], Tcw=a["T"], radius=a["radius"], min_points=a["min_points"],
+                              first=a["first"], count=a["count"], **flt)
+        return vms.mesh(rec, flags, voxel, a["normal"], first=a["first"], count=a["count"], **flt)
+
+    def _query(self, op, a):
+        """one read-only query: its answer from the model's own state, which it leaves as it is"""
+        c, k = self.qcov, op[5:]
+        c["calls"] += 1
+        ref = self._query_refusal(op, a)
+        if ref is not None and ref[1] not in ("small_short", "tri_short"):
+            c["refusals"] += 1
+            c["refuse_no_map_" + k if ref[1] == "no_map" else "refuse_" + ref[1]] += 1
+            return {"refused": ref[0]}
+        now = self.qnow
+        assert _same_state(now, self._query_state()), "the queries' copy of the state is behind the model"
+        exp = self.answer(op, a, now)
+        totals = {f: exp[f] for f in QTOTALS[op]}
+        if ref is not None:  # too short: refused with the totals filled
+            assert totals["small" if op == "vmap_components" else "triangles"] >= 2, (op, totals)
+            c["refusals"] += 1
+            c["refuse_" + ref[1]] += 1
+            return {"refused": ref[0], "totals": totals}
+        rec, flags, _ = now
+        M = len(rec["multiplicity"])
+        c["n_" + k] += 1
+        # sensitivity (counts, never expectations): the answer from the state before the last change, and without the flags
+        if self.qprev is not None:
+            try:
+                c["sens_query_stale_" + k] += _differs(op, self.answer(op, a, self.qprev), exp)
+            except AssertionError:  # (a range that the earlier map does not hold)
+                c["sens_query_stale_" + k] += 1
+        if a["require_published"] and flags is not None and flags.any():
+            c["sens_query_flags_" + k] += _differs(op, self.answer(op, a, (rec, None, now[2])), exp)
+        # conditions on the sequence
+        for e in QEVENTS:
+            c["after_%s_%s" % (e, k)] += self.qlast == ("vmap_" + e, True)
+        for e in QFIRST:  # (big: a map of more than BIG entries, whatever came before)
+            c["first_" + e] += M > BIG if e == "big" else self.qlast[0] == ("set_pose" if e == "set_pose" else "vmap_" + e)
+        if a["require_published"] and M:
+            c[("pub_after_" if self.map.cl.calls else "pub_before_") + k] += 1
+        if op == "vmap_cast_segments":
+            c["rays_hit"] += exp["rays_hit"]
+            c["rays_skipped"] += exp["rays_skipped"]
+            c["rays_miss"] += exp["rays_total"] - exp["rays_hit"] - exp["rays_skipped"]
+        elif op == "vmap_render":
+            c["render_hit_and_zero"] += 0 < exp["rays_hit"] < exp["rays_total"]
+        elif op == "vmap_components":
+            c["comp_rich"] += exp["components"] >= 2 and exp["small"] > 0 and exp["members"] < exp["entries"]
+        elif op == "vmap_normals":
+            c["normals_rich"] += 0 < exp["estimated"] < exp["entries"] and exp["oriented"] > 0
+            self.qnormal = ({f: a[f] for f in ("min_multiplicity", "require_published", "first", "count")}, exp["normal"].copy())
+        else:
+            c["mesh_quads_singles"] += exp["quads"] > 0 and exp["singles"] > 0
+            c["mesh_empty"] += exp["entries"] > 0 and exp["triangles"] == 0
+            c["mesh_" + a["source"]] += 1
+        return {"refused": None, "answer": exp, "totals": totals}
 
     def _map(self, op, a):
         ref = self.refusal(op, a)
@@ -716,10 +883,22 @@ def _plans(rng, w, room):
     return out
 
 
-def generate(seed, w, steps=STEPS):
+def generate(seed, w, steps=STEPS, queries=True):
     """yields (op, args); the caller applies each to the MapWorld (and to an engine) before asking for the next, so every
     draw is a function of the seed and the model's state alone.  Weighted random draws; the gaps the coverage conditions
-    still have are closed with rising urgency as the steps run out (cloud_model.generate's scheme)."""
+    still have are closed with rising urgency as the steps run out (cloud_model.generate's scheme).
+
+    queries: the five read-only queries are interleaved from a stream of their own (QueryStream: a second RNG, counters of
+    its own).  The main stream neither sees nor counts them: with the QUERY_OPS filtered out the sequence is the one that
+    queries=False yields, which tests/test_mapfuzz_cpu.py asserts."""
+    q = QueryStream(seed, w, steps) if queries else None
+    for step, (op, a) in enumerate(_main_stream(seed, w, steps)):
+        yield op, a
+        if q is not None:
+            yield from q.behind(step, op, a)
+
+
+def _main_stream(seed, w, steps):
     rng = np.random.default_rng(9100 + seed)
     p = np.array([_WEIGHT[o] for o in OPS], float)
     p /= p.sum()
@@ -779,6 +958,217 @@ def generate(seed, w, steps=STEPS):
             yield _map_args(rng, w, op, kw)
 
 
+def crafted_normals(rng, n, mode="mixed"):
+    """float32[n, 3] for vmap_mesh, the cases vmap_mesh_np.STATS names: "zero" -- no owner at all; "axis" -- every normal
+    along one axis; "mixed" -- per entry a random normal, an axis-aligned one, a tie of two or of three magnitudes, a zero
+    row, a NaN row or a NaN component"""
+    out = np.zeros((n, 3), F)
+    if mode == "zero":
+        return out
+    if mode == "axis":
+        out[:, int(rng.integers(0, 3))] = rng.choice(np.array([1, -1], F), n)
+        return out
+    out[:] = rng.normal(size=(n, 3))
+    kind = rng.integers(0, 8, n)
+    for i in np.flatnonzero(kind > 1):
+        s = abs(out[i, 0]) + F(0.5)
+        out[i] = {2: (0, 0, s), 3: (0, -s, 0), 4: (s, -s, s / 4), 5: (s, s, -s), 6: (0, 0, 0)}.get(int(kind[i]), (np.nan,) * 3)
+    if n:
+        out[int(rng.integers(0, n)), int(rng.integers(0, 3))] = np.nan
+    return out
+
+
+class QueryStream:
+    """The five read-only queries beside the main stream: what to issue behind the main stream's step that has just been
+    applied.  Draws come from an RNG of its own and the counters are MapWorld.qcov, so the main stream is as it would be
+    without them.  Queries are issued with probability RATE behind any call while a map is open, and steered: behind a
+    repose, a committing retire and a committing classify every kind that has not followed one yet; behind the first clear,
+    import and set_pose and once the map exceeds BIG entries all five; with require_published before the first committing
+    classify of a map and when entries are published; where the content conditions of check_query_coverage are open on a
+    map of more than BIG entries; and the refusals, while they stay below a fifth of the stream's calls."""
+    RATE = 0.02  # (nearly all of a sequence's 60 to 70 queries are steered; EXPERIMENTS.md has what a query costs)
+    TRIES = 5  # of a steered query whose condition may stay open on this map
+
+    def __init__(self, seed, w, steps):
+        self.rng, self.w, self.steps = np.random.default_rng(9300 + seed), w, steps
+        self.tries = {}
+
+    def _try(self, key):
+        self.tries[key] = self.tries.get(key, 0) + 1
+        return self.tries[key] <= self.TRIES
+
+    def behind(self, step, op, a):
+        w, c, rng = self.w, self.w.qcov, self.rng
+        if op == "recon+batch":  # (the call drawn next runs straight behind the overlapped batch: test_gpu_mapfuzz.MapRun.run)
+            return
+        late = 4 * step > 3 * self.steps
+        room = lambda: 5 * (c["refusals"] + 1) <= c["calls"] + (25 if 2 * step < self.steps else 0)
+        if w.map is None:
+            short = [k for k in QKINDS if c["refuse_no_map_" + k] < 1]
+            if short and room():
+                yield self.draw("vmap_" + short[0])
+            return
+        mp, ok = w.map, w.qapplied
+        M = mp.vm.M
+        event = "repose" if ok and op == "vmap_repose" else \
+            op[5:] if ok and op in ("vmap_retire", "vmap_classify") and a["commit"] else None
+        first = [e for e, hit in (("clear", ok and op == "vmap_clear"), ("import", ok and op == "vmap_import"),
+                                  ("set_pose", op == "set_pose"), ("big", M > BIG)) if hit and c["first_" + e] < 1]
+        todo = {}
+        for k in QKINDS:
+            kw = None
+            if first or (event and c["after_%s_%s" % (event, k)] < 1):
+                kw = {}
+            if w.qchanged and M and w.qprev is not None and c["sens_query_stale_" + k] < 1 and self._try(("stale", k)):
+                kw = {}
+            if M and mp.cl.calls == 0 and c["pub_before_" + k] < 1:
+                kw = {"pub": 1}
+            if w.published() > 0 and (c["pub_after_" + k] < 1 or (c["sens_query_flags_" + k] < 1 and self._try(("flags", k)))):
+                kw = {"pub": 1}
+            if late and c["n_" + k] < 3:
+                kw = kw or {}
+            if kw is not None:
+                todo[k] = dict(kw, content=True)
+        if M > BIG:  # the conditions on what the answers hold
+            for key, k, kw in (("rays_hit", "cast_segments", {}), ("rays_miss", "cast_segments", {}),
+                               ("rays_skipped", "cast_segments", {}), ("render_hit_and_zero", "render", {}),
+                               ("comp_rich", "components", {}), ("normals_rich", "normals", {}),
+                               ("mesh_quads_singles", "mesh", {}), ("mesh_from_normals", "mesh", {})):
+                if c[key] < 1 and k not in todo and self._try(key):
+                    todo[k] = dict(kw, content=True)
+                    if k == "mesh" and w.qnormal is None:
+                        todo.setdefault("normals", dict(content=True))
+        for k in QKINDS:  # (normals before the mesh that takes them)
+            if k in todo:
+                yield self.draw("vmap_" + k, **todo[k])
+        for key, mode in (("mesh_empty", "zero"), ("mesh_crafted", "mixed")):
+            if M and c[key] < 1 and (M > BIG or late):
+                yield self.draw("vmap_mesh", crafted=mode)
+        open_ = [r for r in QINVALID if c["refuse_" + r] < 1]
+        if open_ and room():
+            item = self.refused(open_[0] if late or len(open_) == 1 else str(rng.choice(open_)))
+            if item is not None:
+                yield item
+        behind_ = 5 * c["refusals"] > c["calls"]  # (the first refusals came on credit: the stream owes the calls)
+        owing = behind_ or (open_ and not room())
+        if rng.random() < (1 if late and owing else 3 * self.RATE if owing else self.RATE):
+            yield self.draw(str(rng.choice(QUERY_OPS)))
+
+    def refused(self, kind):
+        """a call that must be refused with SDM_EINVAL, or None where this map has none of the kind"""
+        rng, w = self.rng, self.w
+        M = w.map.vm.M
+        if kind == "published2":
+            return self.draw(str(rng.choice(QUERY_OPS)), refuse=kind)
+        if kind == "connectivity":
+            return self.draw("vmap_components", refuse=kind)
+        if kind in ("radius", "twice"):
+            return self.draw("vmap_normals", refuse=kind)
+        if kind == "range":
+            return self.draw(str(rng.choice(["vmap_normals", "vmap_mesh"])), refuse=kind)
+        op, a = self.draw("vmap_components" if kind == "small_short" else "vmap_mesh", refuse=kind)
+        dry = w.answer(op, a, w.qnow)  # the destination is one short of these totals: there must be two at least
+        return (op, a) if M and dry["small" if kind == "small_short" else "triangles"] >= 2 else None
+
+    def segments(self, n):
+        """n segments: the occlusion test of pairs of the log (from the centre of the tag's current pose to the entry),
+        random ones through the map's bounding box, degenerate ones and ones with a coordinate that is not finite"""
+        rng, w = self.rng, self.w
+        mp = w.map
+        xyz = mp.vm.rec["xyz"] if mp is not None else np.zeros((0, 3), F)
+        fin = xyz[np.isfinite(xyz).all(axis=1)]
+        lo, hi = (fin.min(axis=0) - mp.voxel, fin.max(axis=0) + mp.voxel) if len(fin) else (-np.ones(3), np.ones(3))
+        pairs = [i for i in range(mp.ol.E) if int(mp.ol.tag[i]) in w.table] if mp is not None else []
+        centre = {}
+        kinds = rng.choice(4, n, p=[0.45, 0.45, 0.05, 0.05])
+        if n >= 4:
+            kinds[:4] = np.arange(4)
+        O, P = rng.uniform(lo, hi, (n, 3)).astype(F), rng.uniform(lo, hi, (n, 3)).astype(F)
+        for i in range(n):
+            if kinds[i] == 0 and pairs:
+                j = int(rng.choice(pairs))
+                t = int(mp.ol.tag[j])
+                if t not in centre:
+                    centre[t] = carve_np.camera_centre(w.table[t]["T"])
+                O[i], P[i] = centre[t], xyz[int(mp.ol.entry[j])]
+            elif kinds[i] == 2:
+                P[i] = O[i]
+            elif kinds[i] == 3:
+                P[i, int(rng.integers(0, 3))] = rng.choice(np.array([np.nan, np.inf, -np.inf], F))
+        return O, P
+
+    def draw(self, op, content=False, pub=None, crafted=None, refuse=None):
+        """the draw of one query; content: the arguments under which the answer holds the most; pub: require_published;
+        crafted: the mesh's normals; refuse: the argument that is wrong (with no map open every call is refused as it is)"""
+        rng, w = self.rng, self.w
+        mp = w.map
+        M = mp.vm.M if mp is not None else 0
+        plain = content or refuse is not None
+        a = {"min_multiplicity": 0 if plain else int(rng.integers(0, 3)),
+             "require_published": 2 if refuse == "published2" else int(rng.random() < 0.25 and not plain) if pub is None else int(pub),
+             "dest": _dest(rng)}
+
+        def window():
+            a["first"], a["count"] = 0, None
+            if refuse == "range":
+                a["first"], a["count"] = M, 1
+            elif not plain and rng.random() < 0.4:
+                a["first"] = int(rng.integers(0, M + 1))
+                a["count"] = int(rng.integers(0, M - a["first"] + 1))
+
+        if op in ("vmap_cast_segments", "vmap_render"):
+            a.update(start_margin=0 if plain else int(rng.integers(0, 3)), end_margin=0 if plain else int(rng.integers(0, 3)),
+                     max_steps=4096 if plain else int(rng.choice([4096, 65536, 48])))
+        if op == "vmap_cast_segments":
+            n = 130 if content else int(rng.choice([1, 65, int(rng.integers(150, 300))]))
+            a["origins"], a["ends"] = self.segments(n)
+        elif op == "vmap_render":
+            t = int(rng.choice(sorted(t for t in w.table if w.live(t))))
+            T = w.table[t]["T"].copy()
+            if not plain and rng.random() < 0.5:
+                T = jolt(rng, T)
+            c = w.qcov  # (the large view where its hits are still needed: a 9 x 7 view of a sparse map often has none)
+            large = content and (c["render_hit_and_zero"] < 1 or (pub and c["sens_query_flags_render"] < 1))
+            W, H = (33, 17) if large or rng.random() < 0.1 else (9, 7)
+            K = np.array(w.seq.K, F).reshape(4) * np.array([W / cm.W, H / cm.H, W / cm.W, H / cm.H], F)
+            # (the slab lies at depths 1 .. 1.1: rays to depth 1.25 cross it; the restatement's cost grows with their length)
+            a.update(K=K.astype(F), T=T, W=W, H=H, rho_far=0.8 if plain else float(rng.choice([0.8, 0.5, 1.5])))
+        elif op == "vmap_components":
+            a.update(connectivity=12 if refuse == "connectivity" else int(rng.choice([6, 18, 26])),
+                     min_size=4 if content else int(rng.choice([0, 3, 6])))
+            if content and pub is None:
+                a["min_multiplicity"] = 2
+            if refuse == "small_short":
+                a.update(min_size=M + 1, short=True)
+        elif op == "vmap_normals":
+            held = [int(t) for t in w.record_tags() if t in w.table]
+            tags = [t for t in held if plain or rng.random() < 0.7]
+            tags += [t for t in sorted(w.table) if t not in held][:1] or _absent(rng, 1)  # a tag the map does not hold
+            tags = [int(t) for t in rng.permutation(tags)]
+            if refuse == "twice":
+                tags = tags + tags[:1]
+            if not plain and rng.random() < 0.3:
+                tags = None
+            a.update(tags=tags, T=None if tags is None else _table(w, tags)[1], radius=3 if refuse == "radius" else
+                     1 if plain else int(rng.choice([1, 2])), min_points=3 if plain else int(rng.choice([3, 4, 6])))
+            window()
+        else:
+            src = w.qnormal
+            if refuse == "tri_short":
+                a["short"] = True
+            if crafted is None and refuse != "range" and src is not None and (plain or rng.random() < 0.6) and \
+                    (pub is None or src[0]["require_published"] == pub):
+                a.update(src[0], normal=src[1].copy(), source="from_normals")
+            else:
+                window()
+                n = (M - a["first"] if a["count"] is None else a["count"]) if mp is not None else 0
+                mode = crafted or ("axis" if plain else str(rng.choice(["mixed", "axis", "zero"], p=[0.6, 0.3, 0.1])))
+                a.update(normal=crafted_normals(rng, n, mode), source="crafted")
+            if refuse == "published2":
+                a["require_published"] = 2
+        return op, a
+
+
 def online_recipe(w):
     """the online recipe the headers describe, as one fixed sequence: per block integrate, observe, carve, classify; on
     loop closure set_pose, repose, retire, recarve, classify; then records and pairs as from another rank, and the fetches.
@@ -817,6 +1207,41 @@ def online_recipe(w):
     yield "vmap_classify", {"rule": dict(RULE), "commit": 1, "dest": "host"}
     for op in FETCHES:
         yield op, {"ids": None, "first": 0, "count": None, "dest": "host"}
+    # the consumer's step: small components, normals, the mesh from them, the occlusion test of the log's pairs, a view
+    flt = dict(min_multiplicity=0, require_published=0)
+    yield "vmap_components", dict(flt, connectivity=26, min_size=4, dest="host")
+    tags = [int(t) for t in w.record_tags() if t in w.table]
+    yield "vmap_normals", dict(flt, tags=tags, T=_table(w, tags)[1], radius=1, min_points=3, first=0, count=None, dest="device")
+    yield "vmap_mesh", dict(w.qnormal[0], normal=w.qnormal[1].copy(), source="from_normals", dest="device")
+    at = np.flatnonzero(np.isin(mp.ol.tag, sorted(w.table)))  # (the pairs imported as from another rank have no pose here)
+    O = np.stack([carve_np.camera_centre(w.table[int(t)]["T"]) for t in mp.ol.tag[at]]).astype(F)
+    yield "vmap_cast_segments", dict(flt, origins=O, ends=mp.vm.rec["xyz"][mp.ol.entry[at].astype(np.int64)].copy(),
+                                     start_margin=0, end_margin=1, max_steps=4096, dest="host")
+    Wr, Hr = 33, 17
+    K = np.array(seq.K, F).reshape(4) * np.array([Wr / cm.W, Hr / cm.H, Wr / cm.W, Hr / cm.H], F)
+    yield "vmap_render", dict(flt, K=K.astype(F), T=w.table[0]["T"].copy(), W=Wr, H=Hr, rho_far=0.3, start_margin=0, end_margin=0,
+                              max_steps=4096, dest="host")
+
+
+def check_query_coverage(w, seed):
+    """the conditions every sequence's query stream must meet (counted by MapWorld._query, on the model alone)"""
+    c = w.qcov
+    what = "seed %d: %r" % (seed, c)
+    for k in QKINDS:
+        assert c["n_" + k] >= 3, ("query kind %s is answered %d times" % (k, c["n_" + k]), what)
+        for e in QEVENTS:  # straight behind a repose, a committing retire, a committing classify
+            assert c["after_%s_%s" % (e, k)] >= 1, (e, k, what)
+        # with require_published before any classify of the open map and after a committing one
+        assert c["pub_before_" + k] >= 1 and c["pub_after_" + k] >= 1, (k, what)
+        # a query answered from the table or the flags as they were would be noticed
+        assert c["sens_query_stale_" + k] >= 1 and c["sens_query_flags_" + k] >= 1, (k, what)
+    for r in QREFUSALS:
+        assert c[r] >= 1, (r, what)
+    assert 5 * c["refusals"] <= c["calls"], what
+    for key in QCONTENT:
+        assert c[key] >= 1, (key, what)
+    for e in QFIRST:  # all five behind the first clear, import and set_pose, and on a map of more than BIG entries
+        assert c["first_" + e] >= len(QKINDS), (e, what)
 
 
 def check_coverage(w, seed):

@@ -6,8 +6,8 @@ report the largest displacement and the number of keys below their home in the m
 per-call table, and must reach the bounds of the CPU model (table_model), which hold for every insertion order.
 
 The map's sequence runs at the capacity the two imports leave (2048 slots, L = 384: the chain's run covers a fifth of the
-table), so every later call -- integrate, observations, recarve, casts, classify, components, normals, the rebuilds of repose
-and retire -- meets it there; the two further growths come last, each followed by the re-import, the witness and the
+table), so every later call -- integrate, observations, recarve, casts, classify, components, normals, the mesh, the rebuilds
+of repose and retire -- meets it there; the two further growths come last, each followed by the re-import, the witness and the
 read-only queries at the new capacity."""
 import numpy as np
 import pytest
@@ -73,8 +73,12 @@ def kf_upload(eng):
     return pose
 
 
-def queries(eng, ref, chain_cells, pieces, what, out, need=(40, 8, 40)):
-    """the read-only queries at the table as it stands: casts with both margins, a render, components, normals"""
+def queries(eng, ref, chain_cells, pieces, what, out, need=(40, 8, 40),
+            need_mesh=(hm.MIN_MESH_PRESENT_IN_RUN, hm.MIN_MESH_ABSENT_IN_RUN)):
+    """the read-only queries at the table as it stands: casts with both margins, a render, components, normals, the mesh.
+    need: the least chain cells, displaced pieces and absent cells the casts end in; need_mesh: the least cells with and
+    without an entry, homing inside the chain's run, among those the mesh looks up (tests/test_hostile_keys_cpu.py has the
+    model's counts at every capacity)"""
     m = map_model(eng, ref)
     cap = eng.vmap_info()["table_slots"]
     live = chain_cells[np.isin(hk.cell_key(chain_cells), ref.vm.keys.astype(np.uint64))]
@@ -95,8 +99,27 @@ def queries(eng, ref, chain_cells, pieces, what, out, need=(40, 8, 40)):
     for c in (6, 18, 26):
         out.append(comp(eng, "%s components %d" % (what, c), connectivity=c, min_size=4)["label"])
     tags, Tcw = hm.camera_table()
+    estimated = {}
     for r in (1, 2):
-        out.append(normals_run(eng, "%s normals %d" % (what, r), radius=r, tags=tags, Tcw=Tcw)["normal"])
+        estimated[r] = normals_run(eng, "%s normals %d" % (what, r), radius=r, tags=tags, Tcw=Tcw)["normal"]
+        out.append(estimated[r])
+    # the mesh: up to 21 lookups per entry, from the radius-1 normals just computed and along each axis in turn; of the
+    # cells it looks up, some that hold an entry and some that hold none home inside the chain's run
+    from test_gpu_vmap_mesh import host as mesh_host, run as mesh_run   # (that module imports this one)
+    rec = {f: ref.vm.rec[f] for f in ("xyz", "multiplicity")}
+    flags = ref.cl.flags(ref.vm.M) if ref.cl.calls else None
+    inside = [[], []]
+    for i, (name, normal) in enumerate(hm.mesh_normal_sets(ref.vm.M, estimated[1])):
+        p, a, exp = hm.mesh_probes(rec, flags, normal, ref.vm.keys.astype(np.uint64), cap, m["run"])
+        inside[0].append(p)
+        inside[1].append(a)
+        got = mesh_run(eng, "%s mesh, %s normals" % (what, name), normal, device=bool(i & 1))
+        assert got["triangles"] == exp["triangles"] > 0, (what, name, got["triangles"], exp["triangles"])
+        out.append(mesh_host(got["tri"]))
+    have = tuple(len(np.unique(np.concatenate(x), axis=0)) for x in inside)
+    print("%s: of the cells the mesh looks up, %d with and %d without an entry home inside the run %r of %d slots" %
+          ((what,) + have + (m["run"], cap)))
+    assert all(h >= n for h, n in zip(have, need_mesh)), (what, have, need_mesh)
 
 
 def reimport(eng, ref, rec, dst, what, chunk):

@@ -14,7 +14,17 @@ every call of either kind (test_gpu_vmap_repose.same_state: all four infos, a fu
 camera lists, both counters, the flags).  After a refused call and after a commit == 0 call the complete state is
 unchanged (test_gpu_vmap_class.full_state).  Calls whose destinations the binding sizes itself are issued before the model
 computes its answer.  Each sequence must also meet the coverage conditions tests/test_mapfuzz_cpu.py asserts for the
-generator (map_model.check_coverage).  Everything is copied bits or integers: every comparison is for equality."""
+generator (map_model.check_coverage).  Everything is copied bits or integers: every comparison is for equality.
+
+The five read-only queries -- cast_segments, render, components, normals, mesh -- are in the life cycle too, interleaved
+from map_model.QueryStream between any two of the other calls: on maps integrated from pipeline output, with tags that
+outlive their slots, behind set_pose, rehashes, carried and restarted flags, clears and refills.  Each answer equals the
+model's (every array and total, floats as bits), under the rules of the other calls: issued before the model computes its
+answer where the binding sizes the destinations, guarded device destinations sized from the model's answer and clean behind
+their counts; for a small_ids or tri destination one element short, the refusal carries the totals and every byte of every
+destination still holds the guard.  After every query, refused or not, the complete state is unchanged
+(test_gpu_vmap_class.full_state before, state_unchanged after) and then equals the mirror: the queries only read.  Each
+sequence must meet map_model.check_query_coverage as well."""
 import numpy as np
 import pytest
 import torch
@@ -38,7 +48,12 @@ GUARD = 0x5A
 FIELD_DT = {"xyz": np.float32, "pixel": np.uint32, "rho_sigma": np.float32, "intensity": np.uint8, "tag": np.int32,
             "multiplicity": np.uint32, "epoch": np.uint32, "crossings": np.uint64, "ends": np.uint64, "cam_offsets": np.int64,
             "cam_tags": np.int32, "published": np.uint8}
-PER = {"xyz": 3, "rho_sigma": 2}
+PER = {"xyz": 3, "rho_sigma": 2, "normal": 3, "tri": 3}
+QUERY_DT = {"hit_id": np.uint32, "hit_step": np.int32, "hit_rho": np.float32, "label": np.uint32, "size": np.uint32,
+            "small_ids": np.uint32, "normal": np.float32, "variation": np.float32, "points": np.uint32, "tri": np.uint32,
+            "owner_tris": np.uint8, "vertex_used": np.uint8}
+ARG_OF = {"hit_id": "ids", "hit_step": "steps", "hit_rho": "rho", "normal": "normals", "variation": "variations",
+          "points": "counts"}  # the binding's names of the destinations that are not named like the arrays
 _KIND = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
 
 
@@ -49,6 +64,17 @@ def guarded(n, dt, per=1, room=0):
     t = torch.full(((max(n, room) + 3) * per * size,), GUARD, dtype=torch.uint8, device="cuda")
     t = t.view(torch.float32 if np.dtype(dt) == np.float32 else _KIND[size])
     return t.reshape(-1, per) if per > 1 else t
+
+
+def host_guarded(n, dt, per=1):
+    """guarded()'s twin on the host"""
+    a = np.full((n + 3) * per * np.dtype(dt).itemsize, GUARD, np.uint8).view(dt)
+    return a.reshape(-1, per) if per > 1 else a
+
+
+def host_bytes(t):
+    """every byte of a destination of either kind"""
+    return (t.cpu().numpy() if hasattr(t, "cpu") else t).reshape(-1).view(np.uint8)
 
 
 def tail_clean(t, n, what):
@@ -128,6 +154,8 @@ class MapRun(cf.Run):
                     else:
                         self.check_planes(exp["touched"], what)
                         self.check_map(what)
+                elif op in mm.QUERY_OPS:
+                    self.query(op, a, what)
                 else:
                     still = frozen(self.w, op, a)
                     before = full_state(self.eng) if still and self.w.map is not None else None
@@ -152,9 +180,106 @@ class MapRun(cf.Run):
             self.eng.vmap_close()
             self.w.map = None
 
+    def query(self, op, a, what):
+        """one read-only query: its answer against the model's, and the complete state as it was before the call, refused
+        or not"""
+        self.flush()
+        before = full_state(self.eng) if self.w.map is not None else None
+        refused = self.w.refusal(op, a) is not None
+        raw = None
+        if self.runs_blind(op, a) and not a.get("short"):  # (a destination too short is sized from the model's totals)
+            raw = self.engine_map(op, a, None, refused)
+        exp = self.w.apply(op, a)
+        assert bool(exp["refused"]) == refused, what
+        if raw is None:
+            raw = self.engine_map(op, a, exp, refused)
+        self.compare_query(op, a, exp, raw, what)
+        if before is not None:
+            state_unchanged(self.eng, before, what + " (a query only reads)")
+        self.check_map(what)
+
+    def engine_query(self, op, a, exp, refused):
+        """the engine's query: ("err", code, the totals the error carries, destinations) or ("ok", result, device
+        destinations).  Host destinations are the binding's own; device destinations, and both kinds for a call whose
+        small_ids or tri is one element short, are guarded and sized from the model's totals"""
+        eng = self.eng
+        short = bool(a.get("short")) and exp is not None
+        on_device = a["dest"] == "device"
+        sized = exp is not None and (short or (on_device and not refused))
+        tot = exp["totals"] if sized else None
+        make = guarded if on_device else host_guarded
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda() if on_device else x
+        flt = dict(min_multiplicity=a["min_multiplicity"], require_published=a["require_published"])
+        outs = {}
+        if op in ("vmap_cast_segments", "vmap_render"):
+            flt.update(start_margin=a["start_margin"], end_margin=a["end_margin"], max_steps=a["max_steps"])
+            n = len(a["origins"]) if op == "vmap_cast_segments" else a["W"] * a["H"]
+            dest = {}
+            if sized:
+                outs = {f: guarded(n, QUERY_DT[f]) for f in mm.QARRAYS[op]}
+                dest = {ARG_OF[f]: t for f, t in outs.items()}
+            if op == "vmap_render":
+                call = lambda: eng.vmap_render(a["K"], a["T"], a["W"], a["H"], a["rho_far"], **dest, **flt)
+            elif sized:
+                call = lambda: eng.vmap_cast_segments(up(a["origins"]), up(a["ends"]), **dest, **flt)
+            else:
+                call = lambda: eng.vmap_cast_segments(a["origins"], a["ends"], **flt)
+        elif op == "vmap_components":
+            dest = {}
+            if sized:
+                outs = {"label": make(tot["entries"], np.uint32), "size": make(tot["entries"], np.uint32),
+                        "small_ids": make(tot["small"], np.uint32)}
+                dest = dict(labels=outs["label"], sizes=outs["size"],
+                            small_ids=outs["small_ids"][:tot["small"] - 1] if short else outs["small_ids"])
+            call = lambda: eng.vmap_components(connectivity=a["connectivity"], min_size=a["min_size"], **dest, **flt)
+        elif op == "vmap_normals":
+            dest = {}
+            if sized:
+                outs = {f: guarded(tot["entries"], QUERY_DT[f], PER.get(f, 1)) for f in mm.QARRAYS[op]}
+                dest = {ARG_OF[f]: t for f, t in outs.items()}
+            call = lambda: eng.vmap_normals(tags=a["tags"], Tcw=a["T"], radius=a["radius"], min_points=a["min_points"],
+                                            first=a["first"], count=a["count"], **dest, **flt)
+        else:
+            dest, normal = {}, a["normal"]
+            if sized:
+                outs = {"tri": make(tot["triangles"], np.uint32, 3), "owner_tris": make(tot["entries"], np.uint8),
+                        "vertex_used": make(self.w.map.vm.M, np.uint8)}
+                dest = dict(outs, tri=outs["tri"][:tot["triangles"] - 1] if short else outs["tri"])
+                normal = up(normal)
+            call = lambda: eng.vmap_mesh(normal, first=a["first"], count=a["count"], **dest, **flt)
+        if refused:
+            with pytest.raises(self.pkg.SdmError) as e:
+                call()
+            return "err", e.value.code, {f: getattr(e.value, f, None) for f in mm.QTOTALS[op]} if short else None, outs
+        return "ok", call(), outs
+
+    def compare_query(self, op, a, exp, raw, what):
+        if exp["refused"]:
+            assert raw[:2] == ("err", exp["refused"]), (what, raw[:2])
+            if a.get("short"):  # refused with the totals filled, and nothing has been written
+                assert raw[2] == exp["totals"], (what, raw[2], exp["totals"])
+                for f, t in raw[3].items():
+                    assert (host_bytes(t) == GUARD).all(), "%s: %s written by a refused call" % (what, f)
+            return
+        assert raw[0] == "ok", (what, raw)
+        got, outs, ans = raw[1], raw[2], exp["answer"]
+        assert set(got) == set(mm.QARRAYS[op]) | set(mm.QTOTALS[op]), (what, sorted(got))
+        mine, want = {f: int(got[f]) for f in mm.QTOTALS[op]}, {f: int(ans[f]) for f in mm.QTOTALS[op]}
+        assert mine == want, (what, mine, want)
+        for f in mm.QARRAYS[op]:
+            if f == "vertex_used" and f in outs and ans["entries"] == 0:
+                # an empty range queues nothing: the plane of a caller's own destination is not written either
+                assert (host_bytes(outs[f]) == GUARD).all(), "%s: %s written for an empty range" % (what, f)
+                continue
+            same_bits(got[f], ans[f], QUERY_DT[f], "%s %s" % (what, f))
+            if f in outs:
+                tail_clean(outs[f], ans[f].size // PER.get(f, 1), "%s %s" % (what, f))
+
     def engine_map(self, op, a, exp, refused):
         """the engine's call: ("err", code), or ("ok", result, device destinations).  exp: the model's answer when the
         destinations are device tensors, which are sized from it; else None"""
+        if op in mm.QUERY_OPS:
+            return self.engine_query(op, a, exp, refused)
         eng = self.eng
         outs = {}
         if op == "vmap_integrate" and a["dest"] == "none" and not refused:  # (cloud_model draws host and device only)
@@ -305,8 +430,10 @@ def test_random_map_sequences(pkg, oracle, gpu_ok, seed, overlap):
     w = r.w
     print("seed %d overlap %d: %r %r" % (seed, overlap, w.mcov, r.rehashes))
     _seen[seed] = (w.cov["max_voxels"], w.mcov["max_pairs"], r.rehashes["map"], r.rehashes["obs"])
+    print("seed %d overlap %d queries: %r" % (seed, overlap, w.qcov))
     try:  # the counters tests/test_mapfuzz_cpu.py asserts: a later edit cannot hollow the sequences
         mm.check_coverage(w, seed)
+        mm.check_query_coverage(w, seed)
     except AssertionError as e:
         if seed in DEFAULT_SEEDS:
             raise
@@ -330,6 +457,8 @@ def test_table_and_observation_set_outgrow_their_first_slots(pkg, oracle, gpu_ok
 def test_online_recipe(pkg, oracle, gpu_ok, overlap):
     """the recipe the headers describe as one fixed op list (map_model.online_recipe; tests/test_mapfuzz_cpu.py asserts its
     outcomes on the model): integrate, observe, carve, classify per block; set_pose, repose, retire, recarve, classify; then
-    records and pairs as from another rank"""
+    records and pairs as from another rank; then the consumer's step: components, normals, the mesh from them (both on the
+    device), the occlusion test of the log's pairs and a rendered view"""
     r = run_ops(pkg, oracle, 1, overlap, ops=mm.online_recipe)
     assert r.w.mcov["recarve_chain"] == 1 and r.w.mcov["repose_merged"] == 1 and r.rehashes["map"] > 0
+    assert all(r.w.qcov["n_" + k] == 1 for k in mm.QKINDS) and r.w.qcov["mesh_from_normals"] == 1, r.w.qcov

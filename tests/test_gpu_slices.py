@@ -515,18 +515,20 @@ def fuzzed(monkeypatch, module, name, cls, knob, call):
 
 
 MAP_CALLS = ("vmap_integrate", "vmap_observe", "vmap_carve", "vmap_classify", "vmap_import", "vmap_import_observations",
-             "vmap_repose", "vmap_retire", "vmap_recarve") + tuple(mm.FETCHES)
+             "vmap_repose", "vmap_retire", "vmap_recarve") + tuple(mm.FETCHES) + tuple(mm.QUERY_OPS)
 
 
 @pytest.mark.parametrize("lg", [10, 8])
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_map_sequences_in_slices(pkg, oracle, gpu_ok, monkeypatch, seed, lg):
-    """test_gpu_mapfuzz's sequence of the seed, four workgroups per dispatch and one: its comparison with map_model after
-    every call is the check (the same sequence on a default engine is test_random_map_sequences).  Which map calls reach a
-    second dispatch depends on the seed's map sizes; the calls below do for every seed at 2^10 already, and
-    test_online_recipe_in_slices asserts it for every kind"""
+    """test_gpu_mapfuzz's sequence of the seed, the read-only queries of its query stream included, four workgroups per
+    dispatch and one: its comparison with map_model after every call is the check (the same sequence on a default engine
+    is test_random_map_sequences).  Which map calls reach a second dispatch depends on the seed's map sizes; the calls below
+    do for every seed at 2^10 already, and test_online_recipe_in_slices asserts it for every kind"""
     r = fuzzed(monkeypatch, mf, "MapRun", MapRun, {LOG2: lg}, lambda: mf.run_ops(pkg, oracle, seed, False))
     mm.check_coverage(r.w, seed)
+    mm.check_query_coverage(r.w, seed)
+    assert all(r.counts[op][3] >= 3 for op in mm.QUERY_OPS), r.counts
     # every one of these logs outgrows the observation set's first 1024 slots, seed 2's map its first table as well
     # (tests/test_mapfuzz_cpu.py has the model's sizes): the state compared after every call has survived sliced rehashes
     assert r.w.mcov["max_pairs"] > 512 and r.rehashes["obs"] > 0, (r.w.mcov["max_pairs"], r.rehashes)

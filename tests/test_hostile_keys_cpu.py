@@ -8,7 +8,8 @@ The hostile map (voxel 1) is imported in two calls:
   (b) geometric pieces near OFF: a two-layer plane patch, a line, isolated cells, and records that share a cell with
       differing sigma and multiplicity.
 Of the pieces' entries and of the absent cells their queries probe, about L / capacity home inside the chain's run and are
-walked through it.  OFF is chosen so that the counts below hold; they are conditions on the input, not measurements."""
+walked through it; so are the cells sdm_vmap_mesh looks up from its owners, with and without an entry, at every capacity the
+GPU test reaches.  OFF is chosen so that the counts below hold; they are conditions on the input, not measurements."""
 import functools
 
 import numpy as np
@@ -16,6 +17,8 @@ import pytest
 
 import hostile_keys as hk
 import vmap_import_np as vi
+import vmap_mesh_np as vms
+import vmap_normals_np as vn
 import vmap_np
 import vmap_obs_np as vo
 from test_vmap_cast_cpu import both as cast_both
@@ -34,6 +37,11 @@ PIECE_TAGS = (0, 1, 2, 3)
 CAP_PIECES = 2048            # the table's capacity once (b) is in: 2 (L + records of (b)) > 1024
 RECORD_FIELDS = ("xyz", "pixel", "rho_sigma", "intensity", "tag", "multiplicity")
 MIN_PIECES_IN_RUN, MIN_ABSENT_IN_RUN = 20, 200
+# of the distinct cells the mesh looks up, over the four sets of normals the GPU test gives it, those with their home inside
+# the chain's run: with and without an entry.  The mesh looks up some thousands of distinct cells, a few hundred of them
+# pieces' entries, and the run is L / capacity of the table: at 8192 slots, with three quarters of the chain left, 3.5 % --
+# about 10 and 200; the minima are half of that, and hold at 2048 and 4096 slots all the more
+MIN_MESH_PRESENT_IN_RUN, MIN_MESH_ABSENT_IN_RUN = 5, 100
 SET_BITS = 12                # the observation set's chain survives up to 4096 slots; the tests reach 2048
 SET_HEAD, SET_REST = (3, 60), (20, 3)  # its chain: 60 tags on each of entries 0 .. 2, 3 on each of 20 piece entries
 SET_CHAIN = SET_HEAD[0] * SET_HEAD[1] + SET_REST[0] * SET_REST[1]
@@ -152,6 +160,26 @@ def cast_rays(chain_cells, pieces, displaced, absent_in_run):
     P = ((ends + rng.uniform(0.2, 0.8, ends.shape))).astype(F)
     O = ((ends + step + rng.uniform(0.2, 0.8, ends.shape))).astype(F)
     return O, P
+
+
+def axis_normals(M, axis):
+    """float32[M, 3]: every entry's normal along +-e_axis, the sign by the id's parity -- sdm_vmap_mesh then stitches along that
+    axis whatever the geometry is, so between them the three axes walk every direction through the table"""
+    n = np.zeros((M, 3), F)
+    n[:, axis] = 1 - 2 * (np.arange(M) % 2)
+    return n
+
+
+def mesh_probes(rec, flags, normal, keys, cap, run, **kw):
+    """the distinct cells sdm_vmap_mesh looks up for these normals (vmap_mesh_np.mesh's own lookups: the cell below every
+    member, then up to 20 more per owner) whose home at `cap` slots lies inside `run`: (those that hold an entry, those
+    that hold none).  Both kinds are walked through the chain."""
+    probed = []
+    res = vms.mesh(rec, flags, VOXEL, normal, probed=probed, **kw)
+    cells = np.unique(np.concatenate(probed), axis=0)
+    inside = cells[hk.homes_in_run(hk.cell_key(cells), cap, run)]
+    present = np.isin(hk.cell_key(inside), np.asarray(keys, U))
+    return inside[present], inside[~present], res
 
 
 def build_map():
@@ -287,6 +315,36 @@ def test_restatements_agree_with_their_scalar_twins_on_the_hostile_map():
     for margin in (0, 1):
         res = recarve_both(vm, ol, tags, Tcw, end_margin=margin)
     assert res["rays_skipped"] > 0 and res["cells_hit"] > 0 and res["pairs_unposed"] > 0
+
+
+def mesh_normal_sets(M, estimated):
+    """the normals the GPU test stitches the hostile map with: the radius-1 normals estimated on it, then one axis after the
+    other"""
+    return [("estimated", estimated)] + [("axis %d" % ax, axis_normals(M, ax)) for ax in range(3)]
+
+
+def test_mesh_probes_walk_the_chain():
+    """the cells sdm_vmap_mesh looks up from its owners include, at every capacity the GPU test reaches, cells that hold an
+    entry and cells that hold none with their home inside the chain's run; every set of normals gives triangles, and the
+    restatement agrees with its scalar twin on the hostile map"""
+    from test_vmap_mesh_cpu import both as mesh_both
+    vm, cc, pc, da, db = build_map()
+    rec = _records_of(vm)
+    tags, Tcw = camera_table()
+    sets = mesh_normal_sets(vm.M, vn.normals(rec, None, VOXEL, radius=1, tags=tags, Tcw=Tcw)["normal"])
+    for what, normal in sets:
+        res = mesh_both(rec, None, VOXEL, normal)
+        assert res["triangles"] > 0 and res["members"] == vm.M, what
+    for cap in (CAP_PIECES, 2 * CAP_PIECES, 4 * CAP_PIECES):
+        m, keys = layout(vm, cap)
+        present, absent = [], []
+        for what, normal in sets:
+            p, a, _ = mesh_probes(rec, None, normal, keys, cap, m["run"])
+            present.append(p)
+            absent.append(a)
+        have = (len(np.unique(np.concatenate(present), axis=0)), len(np.unique(np.concatenate(absent), axis=0)))
+        print("capacity", cap, "run", m["run"], "probed in run: present, absent", have)
+        assert have[0] >= MIN_MESH_PRESENT_IN_RUN and have[1] >= MIN_MESH_ABSENT_IN_RUN, (cap, have)
 
 
 # ---- the keyframe the GPU test integrates into the hostile map --------------------------------------------------------------

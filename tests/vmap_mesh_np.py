@@ -52,11 +52,12 @@ def axis_of(normal):
     return a, nrm[np.arange(len(nrm)), a]
 
 
-def mesh(rec, flags, voxel_size, normal, min_multiplicity=0, require_published=False, first=0, count=None):
+def mesh(rec, flags, voxel_size, normal, min_multiplicity=0, require_published=False, first=0, count=None, probed=None):
     """rec: the map's records {"xyz" float32[M, 3], "multiplicity" uint32[M]}; flags: uint8[M] or None; normal float32[count,
     3], indexed by id - first -> dict(tri uint32[T, 3], owner_tris uint8[count], vertex_used uint8[M], the seven totals, stats:
     how often each kind of case in STATS occurred, corners int64[count, 3]: (Nu, Nv, C) of every entry of the range with NONE
-    for none, axis int64[count]: a, or NONE for an entry that is no member)"""
+    for none, axis int64[count]: a, or NONE for an entry that is no member).  probed: a list that receives the cells int64[n,
+    3] of every lookup, for the tests that ask which slots of the table a call walks"""
     xyz = np.ascontiguousarray(rec["xyz"], f32).reshape(-1, 3)
     M = len(xyz)
     count = M - first if count is None else count
@@ -79,6 +80,8 @@ def mesh(rec, flags, voxel_size, normal, min_multiplicity=0, require_published=F
         inside = ((c >= -LIM) & (c < LIM)).all(1)
         stats["clipped"] += int((active & ~inside).sum())
         look = active & inside
+        if probed is not None:
+            probed.append(c[look])
         if M and look.any():
             kk = _pack(c[look])
             pos = np.minimum(np.searchsorted(sorted_keys, kk), M - 1)
